@@ -111,16 +111,16 @@ asm: $(FAST_PS)
 probes: build/valu_peak build/valu_ops build/valu_mix build/valu_pair build/valu_bank
 build/valu_bank: tools/gen_valu_bank.py
 	mkdir -p build
-	python3 tools/gen_valu_bank.py
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ tools/valu_bank.hip
+	python3 tools/gen_valu_bank.py build/valu_bank.hip
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ build/valu_bank.hip
 build/valu_pair: tools/gen_valu_pair.py
 	mkdir -p build
-	python3 tools/gen_valu_pair.py
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ tools/valu_pair.hip
+	python3 tools/gen_valu_pair.py build/valu_pair.hip
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ build/valu_pair.hip
 build/valu_mix: tools/gen_valu_mix.py
 	mkdir -p build
-	python3 tools/gen_valu_mix.py
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ tools/valu_mix.hip
+	python3 tools/gen_valu_mix.py build/valu_mix.hip
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ build/valu_mix.hip
 build/valu_%: tools/valu_%.hip
 	mkdir -p build
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $<

@@ -31,8 +31,17 @@ shard, merged on the host):
     measured on the earlier steps (the library keeps the rates), merged on the
     host.  Fewer than N visible devices is an error: exit 2, no JSON line.
     `--multi` forces this path at N = 1.
-Every line carries `n1_config4_ghs`, one configs[3] step searched on one device
+With `--full` every line carries `n1_config4_ghs`, one configs[3] step searched on one device
 alone, and configs[3] lines `per_gpu_efficiency` = value / (N x it).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs the W warmup
+steps, times the K steps and prints the line: `value`, `ms_per_step`, the result
+self-check and the roofline figures that come from the timed launches' own HIP
+events.  `--dump-outputs DIR` also writes what the last timed step returned
+(dump_outputs).  Everything that takes runs of its own -- `n1_config4_ghs`, the
+energy counters, the clock probe, the PMC passes, the power sample and
+`cpu_baseline`, described below -- is measured only with `--full`; without it
+those fields are null.
 
 Rank 0 prints ONE JSON line.  `roofline.frac` is the dominant kernel's
 algorithmic per-nonce work (nonce_ops: the VALU instructions one nonce needs
@@ -202,6 +211,7 @@ class LaunchedSteps:
         self.dist, self.bal = dist, bal
         self.pending = []  # [(k, work, gathered tensors)] in step order
         self.best = None
+        self.last = None
         self.nonces = 0    # this rank's nonces since the last finish()
 
     def _fold(self, item):
@@ -212,6 +222,7 @@ class LaunchedSteps:
         else:
             vals = [out]
         merged = merge((v[0] + (1 << 63), v[1] + (1 << 63)) for v in vals)
+        self.last = merged  # merges fold in step order: the latest step's merged (hash, nonce)
         self.best = merged if self.best is None else merge([self.best, merged])
         if self.bal is not None:
             self.bal.update([(v[2], v[3]) for v in vals])
@@ -779,6 +790,19 @@ def power_sample(search_dev, dev=0, seconds=1.0):
     return out
 
 
+def dump_outputs(path, last_step, timed_min):
+    """--dump-outputs: what a caller of the timed path received, as float64 arrays under `path`.
+    A search returns the (hash, nonce) minimum of its range, two u64; each is written as its high
+    and low 32 bits, [hash >> 32, hash & 0xffffffff, nonce >> 32, nonce & 0xffffffff], so that
+    float64 holds it exactly.  last_step.npy: the last timed step's (merged over the GPUs);
+    timed_min.npy: the minimum over all timed steps, the line's `result`."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, (h, n) in (("last_step", last_step), ("timed_min", timed_min)):
+        np.save(os.path.join(path, name + ".npy"),
+                np.array([h >> 32, h & 0xFFFFFFFF, n >> 32, n & 0xFFFFFFFF], dtype=np.float64))
+
+
 def die(msg, code=2):
     print(f"bench.py: {msg}", file=sys.stderr, flush=True)
     sys.exit(code)
@@ -918,6 +942,12 @@ def main():
     ap.add_argument("--devices", default=None,
                     help="in-process path: comma-separated device list (default 0..N-1); repeats rehearse "
                          "N workers on fewer GPUs, e.g. --gpus 4 --devices 0,0,0,0 on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the one-device configs[3] search "
+                         "(n1_config4_ghs), the energy counters, the clock probe, the rocprofv3 PMC passes, the "
+                         "power sample and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes")
     ap.add_argument("--no-clock", action="store_true",
@@ -927,6 +957,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         die("--gpus and --steps must be >= 1, --warmup >= 0")
+    if not args.full:
+        # a plain run does what the headline figure needs and nothing else: set up, warm up, time
+        # the steps, write the outputs when asked, print the line
+        args.no_cpu_baseline = args.no_pmc = args.no_clock = args.no_n1 = True
     cfg_name = args.config or default_config(args.gpus)
     cfg = dict(CONFIGS[cfg_name])
     if args.msg is not None:
@@ -968,7 +1002,14 @@ def main():
         die(f"libminehip sees {minehip.device_count()} devices, torch {ndev}")
     dist = None
     shared = None
+    line_out = sys.stdout
     if launched:
+        # gloo writes its connection notes to the process's stdout, and those of two ranks interleave
+        # into fragments (a bare "1" among them) that read as JSON.  The line keeps the real stdout;
+        # whatever else this process writes to descriptor 1 from here on goes to stderr.
+        sys.stdout.flush()
+        line_out = os.fdopen(os.dup(1), "w")
+        os.dup2(2, 1)
         import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=world)  # host merge: no RCCL
         pr = torch.cuda.get_device_properties(devs[0])
@@ -992,14 +1033,18 @@ def main():
     pipe = (LaunchedSteps(lambda a, b: minehip.search(msg, a, b, devs[0]), cfg, rank, world, steps, dist, bal)
             if launched else None)
 
+    last = [None]  # what the latest step returned to its caller (--dump-outputs)
+
     def step(k, timed=False):
         if launched:
             pipe.step(k)  # its host merge completes while the next step searches (LaunchedSteps)
             return None
         lo, hi = job_range(cfg, n_gpus, k, steps)
         if multi:
-            return minehip.search_multi(msg, lo, hi, devs)
-        return minehip.search(msg, lo, hi, devs[0])
+            last[0] = minehip.search_multi(msg, lo, hi, devs)
+        else:
+            last[0] = minehip.search(msg, lo, hi, devs[0])
+        return last[0]
 
     barrier = (lambda: dist.barrier()) if launched else (lambda: None)
     for w in range(args.warmup):
@@ -1020,13 +1065,16 @@ def main():
         minehip.profile_enable(d, True)
     # the energy of the timed region itself, per device of this process: counters read just outside
     # it (the window adds only the region's opening barrier and closing sync)
-    meters = {d: energy_meter(d) for d in uniq}
+    meters = {d: energy_meter(d) for d in uniq} if args.full else {}
     e_before = {d: m.read() for d, m in meters.items() if not isinstance(m, dict)}
     r, elapsed = run_timed(lambda k: step(k, timed=True), steps, 0, barrier, torch.cuda.synchronize,
                            finish=pipe.finish if launched else None)
     e_after = {d: meters[d].read() for d in e_before}
     if launched:
         done[devs[0]] += pipe.nonces
+        last[0] = pipe.last
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], r)
     per_dev = []
     for d in uniq:
         pr = minehip.profile_read(d)
@@ -1270,7 +1318,7 @@ def main():
                        # bit-exact against the full-size fixture when one covers the range
                        "golden_ok": None if expect is None else tuple(r) == expect},
         }
-        print(json.dumps(line), flush=True)
+        print(json.dumps(line), file=line_out, flush=True)
     if launched:
         dist.barrier()
         dist.destroy_process_group()

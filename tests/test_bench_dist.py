@@ -55,7 +55,8 @@ def _worker(rank, world, port, cfg, steps, q, balance=False, slow_ns=0, warmup=1
     import torch
     t = torch.tensor([elapsed], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    q.put((rank, r, float(t.item()), mine[warmup:], bal.weights()))  # mine[:warmup]: the warmup steps
+    # mine[:warmup]: the warmup steps; pipe.last: the last step's merged tuple (--dump-outputs)
+    q.put((rank, r, float(t.item()), mine[warmup:], bal.weights(), pipe.last))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -90,6 +91,9 @@ def test_sharded_merge_matches_full_scan(world, scaling):
     assert len({o[2] for o in out}) == 1          # max-over-ranks time agreed
     if scaling == "strong":                       # the timed steps covered [lo, hi] exactly once
         assert _tiles_once(out, lo, hi)
+    # what --dump-outputs writes for the launched path: the last timed step's merge, on every rank
+    last = bench.job_range(cfg, world, steps - 1, steps)
+    assert all(o[5] == oracle.search(MSG, *last) for o in out)
 
 
 def test_balanced_strong_shards_follow_rates():
@@ -309,7 +313,8 @@ def test_cpu_baseline_threads(monkeypatch):
 # paths run here as fresh child processes with two workers on device 0, on configs[3] cut to
 # [0, 2^35 - 1] (fullsize_cfg2.json pins its answer), and must print one good JSON line.
 
-BENCH_N2 = ["--config", "4", "--bits", "35", "--steps", "4", "--warmup", "1", "--no-pmc", "--no-cpu-baseline"]
+BENCH_N2 = ["--full", "--config", "4", "--bits", "35", "--steps", "4", "--warmup", "1", "--no-pmc",
+            "--no-cpu-baseline"]
 
 
 def _run_group(cmd, env, timeout):
@@ -403,15 +408,15 @@ def test_bench_launched_two_ranks_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_one_gpu_line_carries_energy():
-    """`python bench.py` at N = 1 (short): the line names the energy of the clock probe's search
+    """`python bench.py --full` at N = 1 (short): the line names the energy of the clock probe's search
     (`roofline.energy`: J per 10^9 nonces, mean W, the active limit, the power limit, "not exposed"
     where amdsmi has nothing) and of the timed region itself (`energy_timed`), for one device known
     by its PCI address."""
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BENCH_DEVICE"):
         env.pop(k, None)
-    rc, out, err = _run_group([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                               "--no-pmc", "--no-cpu-baseline", "--no-n1"], env, 200)
+    rc, out, err = _run_group([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--steps", "2",
+                               "--warmup", "1", "--no-pmc", "--no-cpu-baseline", "--no-n1"], env, 200)
     assert rc == 0, err[-3000:]
     lines = _json_lines(out)
     assert len(lines) == 1, out[-2000:]
@@ -426,3 +431,52 @@ def test_bench_one_gpu_line_carries_energy():
     t = line["energy_timed"]
     assert t and t["devices"] == 1 and t["shared_device"] is False and 5 < t["j_per_gnonce"] < 200, t
     assert line["per_device"][0]["pci"] and line["per_device"][0]["energy_timed"]["joules"] > 0
+
+
+def _u64_pair(a):
+    """(hash, nonce) back from dump_outputs' float64 [hi32, lo32, hi32, lo32]."""
+    hi, lo, nhi, nlo = (int(x) for x in a)
+    return (hi << 32) | lo, (nhi << 32) | nlo
+
+
+def test_dump_outputs_round_trips_u64(tmp_path):
+    """--dump-outputs writes each (hash, nonce) as float64 halves that hold a u64 exactly, values
+    at and above 2^53 and 2^63 included, and creates the directory."""
+    import numpy as np
+    last, best = ((1 << 64) - 1, (1 << 53) + 1), ((1 << 63) + 12345, 0)
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), last, best)
+    assert sorted(os.listdir(d)) == ["last_step.npy", "timed_min.npy"]
+    for name, want in (("last_step.npy", last), ("timed_min.npy", best)):
+        a = np.load(d / name)
+        assert a.dtype == np.float64 and a.shape == (4,)
+        assert _u64_pair(a) == want
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: one line whose `steps` and
+    `ms_per_step` are those of the timed region, nothing that needs a run of its own (those fields are
+    null without --full), and DIR holding the last step's (hash, nonce), which for configs[1] (every
+    step scans [0, 2^32 - 1]) is the fixture's answer and the line's `result`."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BENCH_DEVICE"):
+        env.pop(k, None)
+    rc, out, err = _run_group([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+                               "--warmup", "1", "--dump-outputs", str(tmp_path)], env, 120)
+    assert rc == 0, err[-3000:]
+    lines = _json_lines(out)
+    assert len(lines) == 1, out[-2000:]
+    line = lines[0]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["dtype"] == "u32"
+    assert abs(line["ms_per_step"] - (1 << 32) / (line["value"] * 1e9) * 1e3) < 0.01 * line["ms_per_step"]
+    assert line["result"]["golden_ok"] is True and line["result"]["rehash_ok"] is True
+    assert 0 < line["roofline"]["frac"] <= 1
+    for k in ("n1_config4_ghs", "cpu_baseline", "energy_timed", "sclk_ghz", "kernel_clock_ghz"):
+        assert line[k] is None, k
+    assert not {"pmc", "power", "kernel_clock", "energy"} & set(line["roofline"])
+    want = (line["result"]["hash"], line["result"]["nonce"])
+    assert want == (3580905509, 4025695320)
+    assert _u64_pair(np.load(tmp_path / "last_step.npy")) == want
+    assert _u64_pair(np.load(tmp_path / "timed_min.npy")) == want

@@ -155,4 +155,6 @@ int main() {
     return 0;
 }
 '''
-open("tools/valu_pair.hip", "w").write(src)
+# the committed copy is the source as measured; `make probes` writes its own under build/
+import sys  # noqa: E402
+open(sys.argv[1] if len(sys.argv) > 1 else "tools/valu_pair.hip", "w").write(src)

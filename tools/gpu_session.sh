@@ -52,25 +52,25 @@ for s in $STEPS; do
       ;;
     bench)
       # the driver's command line (BENCH_rNN.json)
-      timeout -k 10 600 python "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout -k 10 600 python "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
       rc=$?; echo "bench rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench.json"; fatal $rc
       ;;
     multi1)
       # N = 1 through the in-process multi-device path (mh_search_multi, scheduler chunks)
-      timeout -k 10 600 python "$ROOT/bench.py" --gpus 1 --multi --steps 20 --warmup 5 --no-pmc --no-cpu-baseline \
+      timeout -k 10 600 python "$ROOT/bench.py" --full --gpus 1 --multi --steps 20 --warmup 5 --no-pmc --no-cpu-baseline \
           > "$OUT/bench_multi1.json" 2> "$OUT/bench_multi1.err"
       rc=$?; echo "multi1 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench_multi1.json"; fatal $rc
       # the scheduler path itself: 4 worker threads on the one GPU, configs[3] slices (2^38 to stay short)
-      timeout -k 10 600 python "$ROOT/bench.py" --gpus 4 --devices 0,0,0,0 --bits 38 --steps 8 --warmup 1 \
+      timeout -k 10 600 python "$ROOT/bench.py" --full --gpus 4 --devices 0,0,0,0 --bits 38 --steps 8 --warmup 1 \
           > "$OUT/bench_multi4.json" 2> "$OUT/bench_multi4.err"
       rc=$?; echo "multi4 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench_multi4.json"; fatal $rc
-      timeout -k 10 600 python "$ROOT/bench.py" --gpus 1 --config 4 --bits 38 --steps 8 --warmup 1 --no-pmc \
+      timeout -k 10 600 python "$ROOT/bench.py" --full --gpus 1 --config 4 --bits 38 --steps 8 --warmup 1 --no-pmc \
           --no-cpu-baseline > "$OUT/bench_single38.json" 2> "$OUT/bench_single38.err"
       rc=$?; echo "single38 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench_single38.json"; fatal $rc
       ;;
     cfg4)
       # configs[3] (2^40, the scaling workload) on one GPU: 20 slices covering the whole range
-      timeout -k 10 600 python "$ROOT/bench.py" --gpus 1 --config 4 --steps 20 --warmup 1 --no-cpu-baseline \
+      timeout -k 10 600 python "$ROOT/bench.py" --full --gpus 1 --config 4 --steps 20 --warmup 1 --no-cpu-baseline \
           > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"
       rc=$?; echo "cfg4 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench_cfg4.json"; fatal $rc
       ;;
@@ -99,15 +99,15 @@ for s in $STEPS; do
     pmc)
       (cd /tmp && timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace \
           -d "$OUT/pmc1" -o run --output-format csv \
-          -- python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-pmc --no-clock > /dev/null 2> "$OUT/pmc1.err")
+          -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-pmc --no-clock > /dev/null 2> "$OUT/pmc1.err")
       rc=$?; echo "pmc1 rc=$rc" | tee -a "$OUT/session.log"; fatal $rc
       (cd /tmp && timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace \
           -d "$OUT/pmc2" -o run --output-format csv \
-          -- python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-pmc --no-clock > /dev/null 2> "$OUT/pmc2.err")
+          -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-pmc --no-clock > /dev/null 2> "$OUT/pmc2.err")
       rc=$?; echo "pmc2 rc=$rc" | tee -a "$OUT/session.log"; fatal $rc
       (cd /tmp && timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace \
           -d "$OUT/pmc3" -o run --output-format csv \
-          -- python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-pmc --no-clock > /dev/null 2> "$OUT/pmc3.err")
+          -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-pmc --no-clock > /dev/null 2> "$OUT/pmc3.err")
       rc=$?; echo "pmc3 rc=$rc" | tee -a "$OUT/session.log"; fatal $rc
       ;;
     listpmc)
@@ -140,7 +140,7 @@ for s in $STEPS; do
       ;;
     benchcfg)
       for c in 3a 3b; do
-        timeout -k 10 600 python "$ROOT/bench.py" --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > "$OUT/bench_cfg$c.json" 2> "$OUT/bench_cfg$c.err"
+        timeout -k 10 600 python "$ROOT/bench.py" --full --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > "$OUT/bench_cfg$c.json" 2> "$OUT/bench_cfg$c.err"
         rc=$?; echo "bench cfg $c rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench_cfg$c.json"; fatal $rc
       done
       ;;
@@ -171,24 +171,24 @@ for s in $STEPS; do
     dist2)
       # 2 ranks on the box's one GPU: bench.py's launched path (configs[3] layout, 2^36 to stay short)
       BENCH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29533 "$ROOT/bench.py" --gpus 2 --steps 4 --warmup 1 \
+          --master-addr 127.0.0.1 --master-port 29533 "$ROOT/bench.py" --full --gpus 2 --steps 4 --warmup 1 \
           --bits 36 > "$OUT/dist2.json" 2> "$OUT/dist2.err"
       rc=$?; echo "dist2 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/dist2.json"; fatal $rc
       # the same with one GPU visible per rank (a launcher isolating ranks): LOCAL_RANK 1 runs on
       # its only visible device, and the line says two ranks shared it
       HIP_VISIBLE_DEVICES=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29536 "$ROOT/bench.py" --gpus 2 --steps 4 --warmup 1 \
+          --master-addr 127.0.0.1 --master-port 29536 "$ROOT/bench.py" --full --gpus 2 --steps 4 --warmup 1 \
           --bits 36 > "$OUT/dist2_vis.json" 2> "$OUT/dist2_vis.err"
       rc=$?; echo "dist2 per-rank visibility rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/dist2_vis.json"; fatal $rc
       ;;
     dist8)
       # 8 ranks on the box's one GPU: bench.py's N = 8 sharding and host merge (2^36, golden-checked weak line too)
       BENCH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-          --master-addr 127.0.0.1 --master-port 29534 "$ROOT/bench.py" --gpus 8 --steps 4 --warmup 1 \
+          --master-addr 127.0.0.1 --master-port 29534 "$ROOT/bench.py" --full --gpus 8 --steps 4 --warmup 1 \
           --bits 36 > "$OUT/dist8.json" 2> "$OUT/dist8.err"
       rc=$?; echo "dist8 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/dist8.json"; fatal $rc
       BENCH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-          --master-addr 127.0.0.1 --master-port 29535 "$ROOT/bench.py" --gpus 8 --config 2 --bits 28 --steps 2 \
+          --master-addr 127.0.0.1 --master-port 29535 "$ROOT/bench.py" --full --gpus 8 --config 2 --bits 28 --steps 2 \
           --warmup 1 > "$OUT/dist8_weak.json" 2> "$OUT/dist8_weak.err"
       rc=$?; echo "dist8 weak rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/dist8_weak.json"; fatal $rc
       ;;
@@ -196,11 +196,11 @@ for s in $STEPS; do
       # the N = 8 configs[3] lines end to end on the box's one GPU (all 8 workers / ranks share it, so
       # value and per_gpu_efficiency mean nothing here; the point is the whole path and golden_ok):
       # the in-process path (mh_search_multi over 8 listed devices) and the launched path (8 ranks)
-      timeout -k 10 600 python "$ROOT/bench.py" --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 2 \
+      timeout -k 10 600 python "$ROOT/bench.py" --full --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 2 \
           --no-clock > "$OUT/inproc8_cfg4.json" 2> "$OUT/inproc8_cfg4.err"
       rc=$?; echo "inproc8 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/inproc8_cfg4.json"; fatal $rc
       BENCH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-          --master-addr 127.0.0.1 --master-port 29541 "$ROOT/bench.py" --gpus 8 --steps 20 --warmup 2 \
+          --master-addr 127.0.0.1 --master-port 29541 "$ROOT/bench.py" --full --gpus 8 --steps 20 --warmup 2 \
           --no-clock > "$OUT/dist8_cfg4.json" 2> "$OUT/dist8_cfg4.err"
       rc=$?; echo "dist8 cfg4 rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/dist8_cfg4.json"; fatal $rc
       ;;
@@ -208,7 +208,7 @@ for s in $STEPS; do
       # round 5: configs[2]'s 60 x 'x' line with the Early layout (default) and without, PMC passes
       # included: VALU per nonce, issue per quad-cycle and waves per SIMD of each dominant kernel
       for e in 1 0; do
-        MINEHIP_EARLY=$e timeout -k 10 600 python "$ROOT/bench.py" --config 3b --steps 5 --warmup 2 --no-cpu-baseline \
+        MINEHIP_EARLY=$e timeout -k 10 600 python "$ROOT/bench.py" --full --config 3b --steps 5 --warmup 2 --no-cpu-baseline \
             > "$OUT/bench_cfg3b_early$e.json" 2> "$OUT/bench_cfg3b_early$e.err"
         rc=$?; echo "earlypmc $e rc=$rc" | tee -a "$OUT/session.log"; fatal $rc
       done

@@ -1,5 +1,5 @@
-"""Summarise a rocprofv3 PMC session of `bench.py --steps 1 --warmup 0
---no-cpu-baseline` (tools/gpu_session.sh step `pmc`) per kernel:
+"""Summarise a rocprofv3 PMC session of `bench.py --full --steps 1 --warmup 0
+--no-cpu-baseline --no-pmc --no-clock` (tools/gpu_session.sh step `pmc`) per kernel:
 
   VALU instructions per nonce   SQ_INSTS_VALU x 64 / nonces   (cross-check of nonce_ops)
   effective clock (GHz)         GRBM_GUI_ACTIVE / 8 XCDs / kernel time
