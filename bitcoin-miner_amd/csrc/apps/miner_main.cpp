@@ -6,7 +6,10 @@
 // Request (message.go:27-34), scan [Lower, Upper], Write NewResult(hash,
 // nonce) (message.go:38-44).  A Read error (server lost / closed) ends it.
 // The scan is libminehip's mh_miner_handle over every visible GPU (one miner
-// process per GPU: HIP_VISIBLE_DEVICES).  LSP is liblsp440 (wire compatible
+// process per GPU: HIP_VISIBLE_DEVICES).  When more Requests are already queued
+// on the connection (up to 64), they go together through
+// mh_miner_handle_batch -- the small ones in one fused GPU pass -- and their
+// Results are written in arrival order.  LSP is liblsp440 (wire compatible
 // with the reference's lsp package, include/lsp440.h).
 //
 //   minehip-miner <hostport>     the miner over LSP
@@ -23,6 +26,8 @@
 #include "common.hpp"
 
 namespace {
+
+constexpr size_t kMaxBatch = 64;  // payloads taken from the connection's queue for one batch
 
 std::vector<int> all_devices() {
     std::vector<int> d;
@@ -66,6 +71,7 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
     std::vector<uint8_t> buf(1 << 16);
     char out[256];
     int status = 0;
+    std::vector<std::string> more;  // the payloads already queued behind the one just read
     for (;;) {
         size_t n = 0;
         rc = lsp_client_read(c, buf.data(), buf.size(), &n, -1);
@@ -74,19 +80,70 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
             continue;
         }
         if (rc != LSP_OK) break;  // server lost or closed: the miner is done
-        size_t on = 0;
-        const int hr = mh_miner_handle(devs.data(), (int)devs.size(), (const char*)buf.data(), n, out, sizeof out,
-                                       &on);
-        if (hr == MH_ENOTREQ || hr == MH_ERANGE) {  // not a Request, or Lower > Upper: no answer
-            fprintf(stderr, "minehip-miner: ignored a message: %s\n", mh_last_error());
+        // What the connection already holds goes to the GPU as one batch (mh_miner_handle_batch:
+        // the small Requests in one fused pass) instead of one blocking search each.  A read that
+        // finds nothing (or the connection's end, which the next blocking read reports) ends it.
+        more.clear();
+        while (more.size() + 1 < kMaxBatch) {
+            std::vector<uint8_t> b2(4096);
+            size_t n2 = 0;
+            int r2 = lsp_client_read(c, b2.data(), b2.size(), &n2, 0);
+            if (r2 == LSP_ESHORT) {
+                b2.resize(n2);
+                r2 = lsp_client_read(c, b2.data(), b2.size(), &n2, 0);
+            }
+            if (r2 != LSP_OK) break;
+            more.emplace_back((const char*)b2.data(), n2);
+        }
+        if (more.empty()) {  // one payload: the single-request path
+            size_t on = 0;
+            const int hr = mh_miner_handle(devs.data(), (int)devs.size(), (const char*)buf.data(), n, out, sizeof out,
+                                           &on);
+            if (hr == MH_ENOTREQ || hr == MH_ERANGE) {  // not a Request, or Lower > Upper: no answer
+                fprintf(stderr, "minehip-miner: ignored a message: %s\n", mh_last_error());
+                continue;
+            }
+            if (hr != MH_OK) {  // the search failed: leave, so the server reassigns the chunk
+                fprintf(stderr, "minehip-miner: %s\n", mh_last_error());
+                status = 1;
+                break;
+            }
+            if (lsp_client_write(c, (const uint8_t*)out, on) != LSP_OK) break;
             continue;
         }
-        if (hr != MH_OK) {  // the search failed: leave, so the server reassigns the chunk
+        const size_t k = more.size() + 1;
+        std::vector<const char*> ptrs(k);
+        std::vector<size_t> lens(k), olens(k);
+        std::vector<int> st(k);
+        std::vector<char> outs(k * sizeof out);
+        ptrs[0] = (const char*)buf.data();
+        lens[0] = n;
+        for (size_t i = 1; i < k; ++i) {
+            ptrs[i] = more[i - 1].data();
+            lens[i] = more[i - 1].size();
+        }
+        const int hr = mh_miner_handle_batch(devs.data(), (int)devs.size(), ptrs.data(), lens.data(), k, outs.data(),
+                                             sizeof out, olens.data(), st.data());
+        bool stop = false;
+        for (size_t i = 0; i < k && !stop && hr == MH_OK; ++i) {  // Results in arrival order
+            if (st[i] == MH_ENOTREQ || st[i] == MH_ERANGE) {
+                fprintf(stderr, "minehip-miner: ignored a message\n");
+                continue;
+            }
+            if (st[i] != MH_OK) {
+                fprintf(stderr, "minehip-miner: a request failed with %d\n", st[i]);
+                status = 1;
+                stop = true;
+            } else if (lsp_client_write(c, (const uint8_t*)outs.data() + i * sizeof out, olens[i]) != LSP_OK) {
+                stop = true;
+            }
+        }
+        if (hr != MH_OK) {
             fprintf(stderr, "minehip-miner: %s\n", mh_last_error());
             status = 1;
             break;
         }
-        if (lsp_client_write(c, (const uint8_t*)out, on) != LSP_OK) break;
+        if (stop) break;
     }
     lsp_client_close(c);
     return status;

@@ -119,4 +119,24 @@ struct GenArgs {
     uint32_t pad;
 };
 
+// ---- batched search (batch_scan / merge_segments) ----
+// Many small Requests in one launch.  A lane's unit of work is an aligned decade, the ten nonces
+// 10u .. 10u+9: they share their digit count, so u is formatted once for the ten.  A tile is one
+// workgroup: kBlockThreads lanes x kBatchDecades decades = 2,560 nonces, one Partial.  One decade
+// per lane, measured against 2 and 4 (HISTORY.md): a batch of a few small requests has too few
+// larger tiles to fill the device, and a large batch runs as fast with small ones.
+constexpr int kBatchDecades = 1;
+constexpr uint32_t kBatchTileDecades = (uint32_t)kBlockThreads * (uint32_t)kBatchDecades;
+constexpr uint32_t kBatchMaxRequests = 4096;  // requests (segments) of one pass
+constexpr uint32_t kBatchMaxEntries = 8192;   // entries of one pass
+
+// One generic piece of one request.  Its decades first/10 .. (first+count-1)/10 are cut into
+// tiles of kBatchTileDecades; tile tile0 + k of the pass runs decades k * kBatchTileDecades ..
+// of them and writes partials[slot0 + k].  Tiles are ordered by request, slot0 == tile0.
+struct BatchEntry {
+    GenArgs g;            // mid, tail, plen, t; first / count: the entry's nonces
+    uint32_t tile0;       // first tile of the entry in its pass
+    uint32_t slot0;       // first partial slot of the entry in its pass
+};
+
 }  // namespace mh

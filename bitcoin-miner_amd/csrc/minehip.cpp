@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -24,6 +25,7 @@
 #include "../../include/minehip.h"
 #include "../../include/minehip_server.h"
 #include "layout.hpp"
+#include "msgcodec.hpp"
 #include "multi.hpp"
 #include "plan.hpp"
 #include "sched.hpp"
@@ -35,6 +37,10 @@ hipError_t launch_generic_scan(const GenArgs& a, Partial* partials, uint32_t blo
 hipError_t launch_hash_batch(const GenArgs& a, const uint64_t* d_nonces, uint64_t* d_out, uint64_t n,
                              hipStream_t s);
 hipError_t launch_merge(const Partial* partials, uint32_t n, Partial* best, hipStream_t s);
+hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials, uint32_t tiles,
+                             hipStream_t s);
+hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
+                                 hipStream_t s);
 }  // namespace mh
 
 namespace {
@@ -65,6 +71,8 @@ namespace {
 constexpr uint64_t kBatchChunk = 1u << 22;  // nonces per hash_batch transfer
 constexpr int kEventPairs = 512;             // profiled launches buffered before harvesting
 constexpr uint32_t kQueueSlots = 4096;       // work-queue counters per search (one per fast launch)
+constexpr size_t kBatchTableBytes = 4u << 20;  // device tables (and their pinned staging) of the batch passes in flight
+constexpr uint32_t kBatchResults = 1u << 16;   // results of the batch passes in flight
 
 struct Timed {
     hipEvent_t start = nullptr, stop = nullptr;
@@ -96,6 +104,11 @@ struct DevCtx {
     uint32_t poff = 0;  // partials written since the last merge
     uint32_t* d_counters = nullptr;  // work-queue counters, zeroed at each search's start
     uint32_t qoff = 0;               // counters used by this search
+    // batched search (mh_search_batch), allocated by the first batch call
+    uint8_t* d_btab = nullptr;  // the passes' tables: entries, segments, per-tile entry index
+    uint8_t* h_btab = nullptr;  // pinned staging of the same bytes
+    Partial* d_bres = nullptr;  // one result per request of the passes in flight
+    Partial* h_bres = nullptr;  // pinned
     // profiling
     bool prof = false;
     std::vector<Timed> pool;
@@ -406,6 +419,157 @@ int check_common(const uint8_t* msg, size_t len) {
     return MH_OK;
 }
 
+// ---- batched search ----
+
+//   MINEHIP_BATCH_SLOTS    partial slots (tiles) one pass of mh_search_batch may use
+//                          (1..kMaxBlocksPerLaunch, the default): a lower value makes small
+//                          batches run several passes and send their larger requests to the
+//                          fallback path (tests; the results never depend on it)
+uint32_t batch_slots() {
+    if (const char* e = getenv("MINEHIP_BATCH_SLOTS")) {
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (v >= 1 && v <= mh::kMaxBlocksPerLaunch) return (uint32_t)v;
+    }
+    return mh::kMaxBlocksPerLaunch;
+}
+
+inline size_t align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+int batch_init_locked(DevCtx* c) {
+    if (!c->d_btab) MH_HIP(hipMalloc(&c->d_btab, kBatchTableBytes));
+    if (!c->h_btab) MH_HIP(hipHostMalloc(&c->h_btab, kBatchTableBytes, hipHostMallocDefault));
+    if (!c->d_bres) MH_HIP(hipMalloc(&c->d_bres, sizeof(Partial) * kBatchResults));
+    if (!c->h_bres) MH_HIP(hipHostMalloc(&c->h_bres, sizeof(Partial) * kBatchResults, hipHostMallocDefault));
+    return MH_OK;
+}
+
+// The results of the passes enqueued since the last drain, waiting in h_bres for the synchronise.
+struct BatchPending {
+    std::vector<size_t> req_idx;  // in h_bres order
+    size_t toff = 0;              // table bytes in use
+};
+
+int batch_drain(DevCtx* c, const mh::BatchRequest* reqs, BatchPending* pend, mh_result* out) {
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        const int rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    for (size_t k = 0; k < pend->req_idx.size(); ++k) {
+        mh_result& r = out[reqs[pend->req_idx[k]].id];
+        r.hash = c->h_bres[k].hash;
+        r.nonce = c->h_bres[k].nonce;
+    }
+    pend->req_idx.clear();
+    pend->toff = 0;
+    return MH_OK;
+}
+
+// One pass on c->stream: one H2D copy of its tables from the pinned staging, batch_scan,
+// merge_segments, one D2H copy of its results.  No synchronise: the tables and results of
+// successive passes sit behind one another until a buffer is full.
+int batch_run_pass(DevCtx* c, const mh::BatchRequest* reqs, const mh::BatchTables& t, uint32_t slot_cap,
+                   BatchPending* pend, mh_result* out) {
+    if (!mh::batch_tables_ok(t, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t o_seg = align16(ne * sizeof(mh::BatchEntry)), o_tile = o_seg + align16((nreq + 1u) * sizeof(uint32_t));
+    const size_t bytes = o_tile + align16(tiles * sizeof(uint32_t));
+    if (bytes > kBatchTableBytes || nreq > kBatchResults) return fail(MH_EINTERNAL, "internal: batch pass too large");
+    if (pend->toff + bytes > kBatchTableBytes || pend->req_idx.size() + nreq > kBatchResults ||
+        (c->prof && c->used == kEventPairs)) {
+        const int rc = batch_drain(c, reqs, pend, out);
+        if (rc) return rc;
+    }
+    uint8_t* h = c->h_btab + pend->toff;
+    uint8_t* d = c->d_btab + pend->toff;
+    memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+    memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    Timed* tm = nullptr;
+    if (c->prof) {  // the batch launches count in the generic class (mh_profile_read out[4], out[5])
+        tm = &c->pool[(size_t)c->used++];
+        tm->kind = 1;
+        tm->var = 0;
+        MH_HIP(hipEventRecord(tm->start, c->stream));
+    }
+    MH_HIP(mh::launch_batch_scan((const mh::BatchEntry*)d, (const uint32_t*)(d + o_tile), c->d_partials, (uint32_t)tiles,
+                                 c->stream));
+    if (tm) {
+        MH_HIP(hipEventRecord(tm->stop, c->stream));
+        c->cnt[4] += t.nonces;
+    }
+    const size_t roff = pend->req_idx.size();
+    MH_HIP(mh::launch_merge_segments(c->d_partials, (const uint32_t*)(d + o_seg), c->d_bres + roff, (uint32_t)nreq,
+                                     c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_bres + roff, c->d_bres + roff, nreq * sizeof(Partial), hipMemcpyDeviceToHost, c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    pend->toff += bytes;
+    return MH_OK;
+}
+
+// The fused passes of a batch, under the device's lock.
+int batch_run_fused(int dev, const mh::BatchRequest* reqs, const std::vector<mh::BatchItem>& items, int passes,
+                    uint32_t slot_cap, mh_result* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (rc) return rc;
+    BatchPending pend;
+    mh::BatchTables t;
+    for (int p = 0; p < passes && !rc; ++p) {
+        mh::build_batch_tables(reqs, items, p, &t);
+        rc = batch_run_pass(c, reqs, t, slot_cap, &pend, out);
+    }
+    if (!rc) rc = batch_drain(c, reqs, &pend, out);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
+// A fallback request's search: (request, hash, nonce) -> MH_*.
+using BatchFallback = std::function<int(const mh::BatchRequest&, uint64_t*, uint64_t*)>;
+
+int search_batch_impl(int dev, const mh_request* reqs, size_t n, mh_result* out, const BatchFallback& fallback) {
+    std::vector<mh::BatchRequest> valid;
+    valid.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        int st = check_common(reqs[i].msg, reqs[i].len);
+        if (!st && reqs[i].lower > reqs[i].upper) st = fail(MH_ERANGE, "lower > upper");
+        out[i] = mh_result{st, 0, 0, 0};
+        if (st) continue;
+        valid.emplace_back();
+        mh::BatchRequest& r = valid.back();
+        mh::absorb_prefix(reqs[i].msg, reqs[i].len, &r.pre);
+        r.lower = reqs[i].lower;
+        r.upper = reqs[i].upper;
+        r.id = i;
+    }
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchItem> items;
+    mh::plan_batch(valid.data(), valid.size(), plan_opts(), slot_cap, &items);
+    int passes = 0;
+    for (const mh::BatchItem& it : items)
+        if (it.kind == 0) passes = std::max(passes, it.pass + 1);
+    if (passes) {
+        const int rc = batch_run_fused(dev, valid.data(), items, passes, slot_cap, out);
+        if (rc) return rc;
+    }
+    for (const mh::BatchItem& it : items) {
+        if (it.kind != 1) continue;
+        const mh::BatchRequest& r = valid[it.idx];
+        const int rc = fallback(r, &out[r.id].hash, &out[r.id].nonce);
+        if (rc) return rc;
+    }
+    return MH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -492,6 +656,92 @@ int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, u
     std::string err;
     const int r = mh::search_chunks(ndev, msg, len, lower, upper, chunk, csearch, out_hash, out_nonce, &err, start);
     return r ? fail(r, err) : MH_OK;
+}
+
+int mh_search_batch(int dev, const mh_request* reqs, size_t n, mh_result* out) {
+    g_err.clear();
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+    return search_batch_impl(dev, reqs, n, out, [dev](const mh::BatchRequest& r, uint64_t* h, uint64_t* nn) {
+        return search_impl(dev, r.pre, r.lower, r.upper, h, nn);
+    });
+}
+
+int64_t mh_batch_plan(const mh_request* reqs, size_t n, mh_batch_item* out, int64_t cap) {
+    g_err.clear();
+    if (n == 0) return 0;
+    if (!reqs) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<mh::BatchRequest> all(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int rc = check_common(reqs[i].msg, reqs[i].len);
+        if (rc) return rc;
+        if (reqs[i].lower > reqs[i].upper) return fail(MH_ERANGE, "lower > upper");
+        mh::absorb_prefix(reqs[i].msg, reqs[i].len, &all[i].pre);
+        all[i].lower = reqs[i].lower;
+        all[i].upper = reqs[i].upper;
+        all[i].id = i;
+    }
+    std::vector<mh::BatchItem> items;
+    mh::plan_batch(all.data(), n, plan_opts(), batch_slots(), &items);
+    int64_t k = 0;
+    for (const mh::BatchItem& it : items) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = mh_batch_item{it.req, it.first, it.count, it.kind, it.pass, it.slot, it.slots};
+        ++k;
+    }
+    return k;
+}
+
+int mh_miner_handle_batch(const int* devs, int ndev, const char* const* requests, const size_t* lens, size_t n,
+                          char* out, size_t cap_each, size_t* out_lens, int* status) {
+    g_err.clear();
+    if (n == 0) return MH_OK;
+    if (!devs || ndev <= 0 || !requests || !lens || !status) return fail(MH_EINVAL, "bad arguments");
+    std::vector<mh::Msg> msgs(n);
+    std::vector<mh_request> reqs;
+    std::vector<size_t> where;  // reqs[k] is payload where[k]
+    for (size_t i = 0; i < n; ++i) {
+        if (out_lens) out_lens[i] = 0;
+        mh::Msg& m = msgs[i];
+        if (!requests[i]) {
+            status[i] = fail(MH_EINVAL, "bad arguments");
+        } else if (!mh::decode(requests[i], lens[i], &m)) {
+            status[i] = fail(MH_ENOTREQ, "payload is not a JSON bitcoin.Message");
+        } else if (m.type != 1) {
+            status[i] = fail(MH_ENOTREQ, "not a Request");  // message.go:10
+        } else if (m.lower > m.upper) {
+            status[i] = fail(MH_ERANGE, "lower > upper");
+        } else {
+            status[i] = MH_OK;
+            reqs.push_back(mh_request{(const uint8_t*)m.data.data(), m.data.size(), m.lower, m.upper});
+            where.push_back(i);
+        }
+    }
+    if (reqs.empty()) return MH_OK;
+    std::vector<mh_result> res(reqs.size());
+    // fallbacks as mh_miner_handle searches: one device through mh_search's path, several through
+    // mh_search_multi's adaptive split
+    const int rc = search_batch_impl(
+        devs[0], reqs.data(), reqs.size(), res.data(), [&](const mh::BatchRequest& r, uint64_t* h, uint64_t* nn) {
+            if (ndev == 1) return search_impl(devs[0], r.pre, r.lower, r.upper, h, nn);
+            const mh_request& q = reqs[r.id];
+            return mh_search_multi(devs, ndev, q.msg, q.len, q.lower, q.upper, 0, h, nn);
+        });
+    if (rc) return rc;
+    for (size_t k = 0; k < reqs.size(); ++k) {
+        const size_t i = where[k];
+        status[i] = res[k].status;
+        if (res[k].status) continue;
+        const std::string s = mh::encode(2, nullptr, 0, 0, 0, res[k].hash, res[k].nonce);  // NewResult (message.go:38-44)
+        if (out_lens) out_lens[i] = s.size();
+        if (!out || cap_each < s.size()) {
+            status[i] = fail(MH_EINVAL, "output buffer too small");
+            continue;
+        }
+        memcpy(out + i * cap_each, s.data(), s.size());
+    }
+    return MH_OK;
 }
 
 int mh_hash_batch(int dev, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n, uint64_t* out_hashes) {

@@ -546,4 +546,109 @@ void plan_search(const Prefix& pre, uint64_t lower, uint64_t upper, const PlanOp
     flush_generic();
 }
 
+// ---- batched search ----
+
+uint64_t batch_tiles(uint64_t first, uint64_t count) {
+    const uint64_t last = first + (count - 1u);
+    const uint64_t decades = last / 10u - first / 10u + 1u;  // <= 2^64 / 10: no overflow below
+    return (decades + (kBatchTileDecades - 1u)) / kBatchTileDecades;
+}
+
+void plan_batch(const BatchRequest* reqs, size_t n, const PlanOpts& opt, uint32_t slot_cap,
+                std::vector<BatchItem>* items) {
+    items->clear();
+    slot_cap = std::min(slot_cap, kMaxBlocksPerLaunch);
+    int pass = 0;
+    uint32_t used_slots = 0, used_reqs = 0, used_entries = 0;
+    std::vector<BatchItem> mine;  // the entries of one request
+    for (size_t i = 0; i < n; ++i) {
+        const BatchRequest& r = reqs[i];
+        mine.clear();
+        bool fused = true;
+        uint64_t tiles = 0;
+        plan_search(r.pre, r.lower, r.upper, opt, [&](const Piece& p) {
+            if (p.kind != 1 || mine.size() == kBatchMaxEntries) return fused = false;
+            const uint64_t t = batch_tiles(p.first, p.count);
+            tiles += t;
+            if (tiles > slot_cap) return fused = false;
+            mine.push_back(BatchItem{r.id, p.first, p.count, 0, 0, 0, (uint32_t)t, i});
+            return true;
+        });
+        if (!fused) {
+            items->push_back(BatchItem{r.id, r.lower, r.upper - r.lower + 1u, 1, -1, 0, 0, i});
+            continue;
+        }
+        if (used_reqs && (used_slots + tiles > slot_cap || used_reqs == kBatchMaxRequests ||
+                          used_entries + mine.size() > kBatchMaxEntries)) {
+            ++pass;
+            used_slots = used_reqs = used_entries = 0;
+        }
+        for (BatchItem& it : mine) {
+            it.pass = pass;
+            it.slot = used_slots;
+            used_slots += it.slots;
+            items->push_back(it);
+        }
+        ++used_reqs;
+        used_entries += (uint32_t)mine.size();
+    }
+}
+
+void build_batch_tables(const BatchRequest* reqs, const std::vector<BatchItem>& items, int pass, BatchTables* out) {
+    out->entries.clear();
+    out->tile_entry.clear();
+    out->seg.clear();
+    out->req_idx.clear();
+    out->nonces = 0;
+    uint32_t slots = 0;
+    for (const BatchItem& it : items) {
+        if (it.kind != 0 || it.pass != pass) continue;
+        if (out->req_idx.empty() || out->req_idx.back() != it.idx) {
+            out->req_idx.push_back(it.idx);
+            out->seg.push_back(it.slot);
+        }
+        BatchEntry e;
+        make_gen_args(reqs[it.idx].pre, &e.g);
+        e.g.first = it.first;
+        e.g.count = it.count;
+        e.tile0 = it.slot;
+        e.slot0 = it.slot;
+        out->tile_entry.insert(out->tile_entry.end(), it.slots, (uint32_t)out->entries.size());
+        out->entries.push_back(e);
+        out->nonces += it.count;
+        slots = it.slot + it.slots;
+    }
+    out->seg.push_back(slots);
+}
+
+bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap) {
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    if (tiles == 0 || tiles > slot_cap || tiles > kMaxBlocksPerLaunch) return false;
+    if (t.entries.empty() || t.entries.size() > kBatchMaxEntries || t.entries.size() > tiles) return false;
+    if (nreq == 0 || nreq > kBatchMaxRequests || nreq > t.entries.size() || t.seg.size() != nreq + 1u) return false;
+    // entries: in tile order, each with exactly its tiles, together all tiles
+    uint64_t next = 0;
+    for (const BatchEntry& e : t.entries) {
+        if (e.g.count == 0 || e.g.first + (e.g.count - 1u) < e.g.first || e.g.t > 63u) return false;
+        if (e.tile0 != next || e.slot0 != e.tile0) return false;
+        next += batch_tiles(e.g.first, e.g.count);
+        if (next > tiles) return false;
+    }
+    if (next != tiles) return false;
+    // tiles: each inside its entry's tiles
+    for (size_t i = 0; i < tiles; ++i) {
+        const uint32_t ei = t.tile_entry[i];
+        if (ei >= t.entries.size()) return false;
+        const BatchEntry& e = t.entries[ei];
+        if (i < e.tile0 || i - e.tile0 >= batch_tiles(e.g.first, e.g.count)) return false;
+    }
+    // segments: contiguous, non-empty, each starting at an entry, together all slots
+    if (t.seg.front() != 0 || t.seg.back() != tiles) return false;
+    for (size_t r = 0; r < nreq; ++r) {
+        if (t.seg[r] >= t.seg[r + 1]) return false;
+        if (t.entries[t.tile_entry[t.seg[r]]].tile0 != t.seg[r]) return false;
+    }
+    return true;
+}
+
 }  // namespace mh

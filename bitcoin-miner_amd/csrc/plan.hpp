@@ -154,4 +154,51 @@ struct Span {
 // positions); a span whose share rounds to no nonce is empty.
 void split_by_cost(const std::vector<CostSeg>& segs, const std::vector<double>& w, std::vector<Span>* out);
 
+// ---- batched search (mh_search_batch / mh_batch_plan) ----
+// Many small Requests in one launch of batch_scan (layout.hpp BatchEntry).  plan_search runs per
+// request: a request whose plan holds only generic pieces is fused, one entry per piece; one with
+// a fast piece, or with more tiles or entries than a pass holds, is a fallback and runs through
+// the single-search path afterwards.  A pass packs whole fused requests, in request order, until
+// it runs out of partial slots (slot_cap), requests (kBatchMaxRequests) or entries
+// (kBatchMaxEntries); a request never spans passes.
+struct BatchRequest {
+    Prefix pre;
+    uint64_t lower, upper;  // lower <= upper
+    uint64_t id;            // the caller's index of the request (BatchItem::req)
+};
+
+struct BatchItem {
+    uint64_t req;           // BatchRequest::id
+    uint64_t first, count;  // fused: the entry's nonces; fallback: the request's (count mod 2^64)
+    int kind;               // 0 fused, 1 fallback
+    int pass;               // fused: its pass, from 0; fallback: -1
+    uint32_t slot, slots;   // fused: the entry's first partial slot in its pass and its tiles; fallback: 0
+    size_t idx;             // position of the request in the array given to plan_batch
+};
+
+// Tiles of an entry: its aligned decades first/10 .. (first+count-1)/10 in tiles of
+// kBatchTileDecades.  count >= 1 and first + (count - 1) <= 2^64 - 1.
+uint64_t batch_tiles(uint64_t first, uint64_t count);
+
+// One item per entry of a fused request and one per fallback request, in request order.
+void plan_batch(const BatchRequest* reqs, size_t n, const PlanOpts& opt, uint32_t slot_cap,
+                std::vector<BatchItem>* items);
+
+// The device tables of one pass.
+struct BatchTables {
+    std::vector<BatchEntry> entries;
+    std::vector<uint32_t> tile_entry;  // per tile: its entry
+    std::vector<uint32_t> seg;         // per request of the pass: its first slot; then the pass's slot count
+    std::vector<size_t> req_idx;       // per request of the pass: its position (BatchItem::idx)
+    uint64_t nonces = 0;
+};
+// From the items of pass `pass` (items as plan_batch wrote them).
+void build_batch_tables(const BatchRequest* reqs, const std::vector<BatchItem>& items, int pass, BatchTables* out);
+
+// What batch_scan and merge_segments rely on, checked before every launch: slots within slot_cap,
+// every tile's entry in range and the tile inside that entry's tiles, entries non-empty with
+// exactly batch_tiles slots and no overflow of their last nonce, segments contiguous and
+// non-empty and together all slots.
+bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap);
+
 }  // namespace mh

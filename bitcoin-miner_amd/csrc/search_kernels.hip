@@ -15,6 +15,11 @@
 //   merge_partials        folds per-workgroup (hash, nonce) candidates into
 //                         the search's running minimum (one 1024-thread
 //                         workgroup).
+//   batch_scan            many small Requests in one launch: one workgroup per
+//                         2,560-nonce tile of a table of entries, one lane = aligned
+//                         decades of ten nonces formatted once (mh_search_batch).
+//   merge_segments        one workgroup per request of a batch pass folds that
+//                         request's slot segment into its result.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -142,6 +147,156 @@ __global__ __launch_bounds__(kMergeThreads) void merge_partials(const Partial* _
         const Partial b = *best;
         if (lex_less(h, nn, b.hash, b.nonce)) *best = Partial{h, nn};
     }
+}
+
+// ---------------------------------------------------------------------------
+// batched search: many small Requests in one launch
+// ---------------------------------------------------------------------------
+namespace dev {
+
+// The ten nonces 10u .. 10u+9 of one aligned decade, digits jlo .. jhi of them (jlo > jhi: none),
+// folded into the lane's running (bh, bn).  All ten have digits(u) + 1 digits (one for u = 0), so
+// the tail image, the one- or two-block choice and the length words are made once; only the last
+// digit's byte changes.  With two tail blocks and the last digit in the second, block 0 is
+// compressed once for the ten.
+__device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32_t jlo, uint32_t jhi, uint64_t& bh,
+                                            uint64_t& bn) {
+    // digits of u; u <= (2^64 - 1) / 10 has at most 19
+    constexpr uint64_t P10[19] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
+                                  100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull,
+                                  10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
+                                  100000000000000000ull, 1000000000000000000ull};
+    uint32_t nu = 0;  // Go %d of 10u + j: no leading zeros, so u = 0 contributes no digit
+#pragma unroll
+    for (int k = 0; k < 19; ++k) nu += (u >= P10[k]) ? 1u : 0u;
+    uint32_t w[32];
+#pragma unroll
+    for (int x = 0; x < 16; ++x) w[x] = a.tail[x];
+#pragma unroll
+    for (int x = 16; x < 32; ++x) w[x] = 0u;
+    uint64_t q = u;
+#pragma unroll
+    for (int k = 0; k < 19; ++k) {
+        if ((uint32_t)k < nu) {
+            const uint64_t q10 = q / 10u;
+            const uint32_t dg = (uint32_t)(q - q10 * 10u);
+            q = q10;
+            const uint32_t pos = a.t + nu - 1u - (uint32_t)k;
+            add_word(w, pos >> 2, (0x30u + dg) << (24u - 8u * (pos & 3u)));
+        }
+    }
+    const uint32_t last = a.t + nu;  // tail byte of the last digit: '0' here, the digit is or-ed in per nonce
+    const uint32_t lsh = 24u - 8u * (last & 3u);
+    add_word(w, last >> 2, 0x30u << lsh);
+    const uint32_t end = last + 1u;  // tail length; the 0x80 byte goes here
+    add_word(w, end >> 2, 0x80u << (24u - 8u * (end & 3u)));
+    const uint64_t bits = (a.plen + nu + 1u) * 8u;
+    const bool two = end + 9u > 64u;
+    const uint32_t bhi = (uint32_t)(bits >> 32), blo = (uint32_t)bits;
+    w[14] = two ? w[14] : bhi;
+    w[15] = two ? w[15] : blo;
+    w[30] = two ? bhi : 0u;
+    w[31] = two ? blo : 0u;
+    // the block the last digit sits in varies per nonce; with two blocks it is block 1 (block 0
+    // then compressed here, once) or block 0 (both blocks per nonce)
+    const bool in1 = last >= 64u;
+    const bool both = two && !in1;
+    const uint32_t jw = (last >> 2) & 15u;
+    uint32_t st[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = a.mid[i];
+    if (in1) sha256_block(st, w);
+    uint32_t v[16];
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+        // both words read first: a select between two elements of w becomes a load through a
+        // selected address, which keeps w out of registers (128 bytes of scratch)
+        const uint32_t lo = w[x], hi = w[16 + x];
+        v[x] = in1 ? hi : lo;
+    }
+    const uint32_t w16 = w[16];
+    const uint64_t n0 = u * 10u;
+#pragma unroll 1
+    for (uint32_t j = jlo; j <= jhi; ++j) {
+        const uint32_t dj = j << lsh;
+        uint32_t x[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) x[i] = v[i] | ((jw == (uint32_t)i) ? dj : 0u);
+        uint32_t s[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s[i] = st[i];
+        if (both) {
+            // block 1 is then padding only: the 0x80 byte if the tail ends at byte 64, and the
+            // length (three live values instead of sixteen registers: 4 waves per SIMD, not 3)
+            sha256_block(s, x);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) x[i] = 0u;
+            x[0] = w16;
+            x[14] = bhi;
+            x[15] = blo;
+        }
+        uint32_t h0, h1;
+        sha256_block_h01(s, x, h0, h1);
+        const uint64_t hash = ((uint64_t)h0 << 32) | h1, n = n0 + j;
+        if (lex_less(hash, n, bh, bn)) {
+            bh = hash;
+            bn = n;
+        }
+    }
+}
+
+}  // namespace dev
+
+// One workgroup per tile of the pass; tile i runs kBatchTileDecades decades of its entry and
+// writes partials[i].  The entry index comes from the host's per-tile table through
+// readfirstlane, so the entry's fields are scalar loads.  No atomics, no counters and no
+// dependency between workgroups: the grid always drains.
+__global__ __launch_bounds__(kBlockThreads) void batch_scan(const BatchEntry* __restrict__ entries,
+                                                            const uint32_t* __restrict__ tile_entry,
+                                                            Partial* __restrict__ partials) {
+    using namespace dev;
+    const uint32_t ei = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_entry[blockIdx.x]);
+    const BatchEntry& e = entries[ei];
+    const GenArgs& a = e.g;
+    // decades of the entry, and the digits of its first and last decade that lie in the range
+    // (first + count and 10u + 9 overflow at the top of u64; last = first + (count - 1) does not)
+    const uint64_t first = a.first, lastn = a.first + (a.count - 1u);
+    const uint64_t u_first = first / 10u, u_last = lastn / 10u;
+    const uint32_t j_first = (uint32_t)(first - u_first * 10u), j_last = (uint32_t)(lastn - u_last * 10u);
+    const uint64_t nd = u_last - u_first + 1u;  // >= 1; offsets below it are decades of the entry
+    const uint64_t base = (uint64_t)(blockIdx.x - e.tile0) * kBatchTileDecades;
+    uint64_t bh = ~0ull, bn = ~0ull;
+#pragma unroll 1
+    for (int k = 0; k < kBatchDecades; ++k) {
+        const uint64_t off = base + (uint32_t)k * (uint32_t)kBlockThreads + threadIdx.x;
+        if (off < nd) {
+            const uint64_t u = u_first + off;
+            scan_decade(a, u, off == 0u ? j_first : 0u, u == u_last ? j_last : 9u, bh, bn);
+        }
+    }
+    block_min(bh, bn);
+    if (threadIdx.x == 0) partials[blockIdx.x] = Partial{bh, bn};
+}
+
+// One workgroup per request of the pass: results[r] = the lexicographic minimum of
+// partials[seg[r] .. seg[r + 1]) (never empty; the host checks the table before the launch).
+__global__ __launch_bounds__(kBlockThreads) void merge_segments(const Partial* __restrict__ partials,
+                                                                const uint32_t* __restrict__ seg,
+                                                                Partial* __restrict__ results) {
+    using namespace dev;
+    const uint32_t r = blockIdx.x;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r]);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r + 1]);
+    uint64_t h = ~0ull, n = ~0ull;
+    for (uint32_t i = a + threadIdx.x; i < b; i += kBlockThreads) {
+        const Partial x = partials[i];
+        if (lex_less(x.hash, x.nonce, h, n)) {
+            h = x.hash;
+            n = x.nonce;
+        }
+    }
+    block_min(h, n);
+    if (threadIdx.x == 0) results[r] = Partial{h, n};
 }
 
 // ---------------------------------------------------------------------------
@@ -274,6 +429,20 @@ hipError_t launch_hash_batch(const GenArgs& a, const uint64_t* d_nonces, uint64_
                              hipStream_t s) {
     const uint64_t blocks = (n + kBlockThreads - 1) / kBlockThreads;
     hipLaunchKernelGGL(hash_batch, dim3((uint32_t)blocks), dim3(kBlockThreads), 0, s, a, d_nonces, d_out, n);
+    return hipGetLastError();
+}
+
+// One pass of a batch: tiles workgroups of batch_scan, then requests workgroups of merge_segments
+// (the caller has checked the tables, minehip.cpp run_pass).
+hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials, uint32_t tiles,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(batch_scan, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL(merge_segments, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, results);
     return hipGetLastError();
 }
 

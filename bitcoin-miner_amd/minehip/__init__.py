@@ -7,6 +7,8 @@ tests read like the reference (line numbers into the reference repo):
   hash_batch(msg, nonces)    the same for many nonces
   search(msg, lower, upper)  the miner scan (stub miner.go:33)
   search_multi(...)          the scan sharded over several devices
+  search_batch(requests)     many small scans fused into one GPU pass
+  miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
   miner_handle(request)      one miner step: Request payload -> Result payload
@@ -20,6 +22,7 @@ import numpy as np
 from ._lib import lib, mh_piece, mh_message, mh_kernel_stat, mh_span, OPS_PER_BLOCK, EXPORTS, LIB_PATH  # noqa: F401
 from ._lib import MH_OK, MH_EINVAL, MH_ERANGE, MH_ETOOLONG, MH_ENODEV, MH_EHIP  # noqa: F401
 from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
+from ._lib import mh_request, mh_result, mh_batch_item  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -62,6 +65,66 @@ def search_multi(msg, lower, upper, devs=None, chunk=0):
     _check(lib.mh_search_multi(arr, len(devs), m, len(m), lower, upper, chunk, ctypes.byref(h),
                                ctypes.byref(n)))
     return h.value, n.value
+
+
+def _requests(requests):
+    """(msg, lower, upper) triples -> (mh_request array, the message bytes it points into)."""
+    keep = []
+    arr = (mh_request * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        try:
+            msg, lower, upper = r
+        except (TypeError, ValueError):
+            raise ValueError(f"request {i}: expected (msg, lower, upper), got {r!r}") from None
+        for name, v in (("lower", lower), ("upper", upper)):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U64_MAX:
+                raise ValueError(f"request {i}: {name} = {v!r} is not a uint64")
+        m = _b(msg)
+        keep.append(m)
+        arr[i].msg, arr[i].len, arr[i].lower, arr[i].upper = m, len(m), lower, upper
+    return arr, keep
+
+
+_REQUEST_ERRORS = {MH_EINVAL: "msg is NULL", MH_ERANGE: "lower > upper",
+                   MH_ETOOLONG: "message longer than MH_MAX_MSG_LEN"}
+
+
+def search_batch(requests, dev=0, errors="raise"):
+    """[(hash, nonce), ...] of many (msg, lower, upper) requests, each exactly what search() gives,
+    with the small ones fused into one GPU pass (mh_search_batch).  A request that fails alone
+    (lower > upper, message too long) raises MinehipError naming its index, or with
+    errors="return" leaves that MinehipError in its place in the list."""
+    if errors not in ("raise", "return"):
+        raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
+    requests = list(requests)
+    arr, keep = _requests(requests)
+    out = (mh_result * max(1, len(requests)))()
+    _check(lib.mh_search_batch(dev, arr, len(requests), out))
+    res = []
+    for i in range(len(requests)):
+        if out[i].status == MH_OK:
+            res.append((out[i].hash, out[i].nonce))
+            continue
+        e = MinehipError(out[i].status, f"request {i}: {_REQUEST_ERRORS.get(out[i].status, 'failed')}")
+        e.index = i
+        if errors == "raise":
+            raise e
+        res.append(e)
+    return res
+
+
+def batch_plan(requests, cap=1 << 16):
+    """Host-only: how search_batch would run the requests -- one dict per entry of a fused request
+    (kind 0: its pass, first partial slot and tiles) and one per fallback request (kind 1)."""
+    requests = list(requests)
+    arr, keep = _requests(requests)
+    buf = (mh_batch_item * cap)()
+    k = lib.mh_batch_plan(arr, len(requests), buf, cap)
+    if k < 0:
+        _check(k)
+    if k > cap:
+        raise ValueError("batch plan longer than cap")
+    return [{f: getattr(buf[i], f) for f, _ in mh_batch_item._fields_} for i in range(k)]
 
 
 def hash_batch(msg, nonces, dev=0):
@@ -209,6 +272,36 @@ def miner_handle(request_payload, devs=(0,)):
     buf = ctypes.create_string_buffer(256)
     _check(lib.mh_miner_handle(arr, len(devs), p, len(p), buf, 256, ctypes.byref(need)))
     return buf.raw[:need.value]
+
+
+def miner_handle_batch(payloads, devs=(0,), errors="return"):
+    """miner_handle for the payloads a miner holds at once (mh_miner_handle_batch): the valid
+    small Requests run as one fused batch on devs[0].  A list with, per payload, the Result
+    payload or the MinehipError miner_handle would raise (MH_ENOTREQ, MH_ERANGE: a miner skips
+    those); errors="raise" raises the first one instead."""
+    if errors not in ("raise", "return"):
+        raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
+    ps = [_b(p) for p in payloads]
+    n, cap = len(ps), 256
+    arr = (ctypes.c_int * len(devs))(*devs)
+    reqs = (ctypes.c_char_p * max(1, n))(*ps)
+    lens = (ctypes.c_size_t * max(1, n))(*[len(p) for p in ps])
+    out = ctypes.create_string_buffer(max(1, n) * cap)
+    out_lens = (ctypes.c_size_t * max(1, n))()
+    status = (ctypes.c_int * max(1, n))()
+    _check(lib.mh_miner_handle_batch(arr, len(devs), reqs, lens, n, out, cap, out_lens, status))
+    what = {MH_ENOTREQ: "not a Request", MH_ERANGE: "lower > upper"}
+    res = []
+    for i in range(n):
+        if status[i] == MH_OK:
+            res.append(out.raw[i * cap:i * cap + out_lens[i]])
+            continue
+        e = MinehipError(status[i], f"payload {i}: {what.get(status[i], 'failed')}")
+        e.index = i
+        if errors == "raise":
+            raise e
+        res.append(e)
+    return res
 
 
 # ---- bitcoin/server/server.go (stub :62) mirror: include/minehip_server.h ----

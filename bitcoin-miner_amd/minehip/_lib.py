@@ -33,7 +33,7 @@ EXPORTS = (
     "mh_abi_version", "mh_device_count", "mh_search", "mh_search_multi", "mh_hash_batch",
     "mh_last_error", "mh_msg_encode", "mh_msg_decode", "mh_miner_handle",
     "mh_profile_enable", "mh_profile_read", "mh_profile_kernels", "mh_plan", "mh_multi_plan",
-    "mh_multi_rates",
+    "mh_multi_rates", "mh_search_batch", "mh_batch_plan", "mh_miner_handle_batch",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -59,6 +59,22 @@ class mh_kernel_stat(ctypes.Structure):
 class mh_span(ctypes.Structure):
     _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("worker", ctypes.c_int32),
                 ("kind", ctypes.c_int32), ("cost", ctypes.c_double)]
+
+
+class mh_request(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t), ("lower", ctypes.c_uint64),
+                ("upper", ctypes.c_uint64)]
+
+
+class mh_result(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("hash", ctypes.c_uint64),
+                ("nonce", ctypes.c_uint64)]
+
+
+class mh_batch_item(ctypes.Structure):
+    _fields_ = [("req", ctypes.c_uint64), ("first", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("kind", ctypes.c_int32), ("pass", ctypes.c_int32), ("slot", ctypes.c_uint32),
+                ("slots", ctypes.c_uint32)]
 
 
 class mh_message(ctypes.Structure):
@@ -122,6 +138,10 @@ def _load():
     L.mh_multi_plan.argtypes = [u8p, sz, u64, u64, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                 ctypes.POINTER(mh_span), ctypes.c_int64]
     L.mh_multi_rates.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
+    L.mh_search_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_result)]
+    L.mh_batch_plan.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_batch_item), ctypes.c_int64]
+    L.mh_miner_handle_batch.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz,
+                                        ctypes.c_char_p, sz, ctypes.POINTER(sz), intp]
     vp = ctypes.c_void_p
     i64 = ctypes.c_int64
     L.mh_sched_default_opts.argtypes = [ctypes.POINTER(mh_sched_opts)]
@@ -141,7 +161,7 @@ def _load():
     L.mh_server_lost.argtypes = [vp, i64, u64]
     L.mh_server_pop_write.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_char_p, sz, ctypes.POINTER(sz)]
     L.mh_server_stats.argtypes = [vp, ctypes.POINTER(mh_sched_stats)]
-    restype = {"mh_plan": ctypes.c_int64, "mh_multi_plan": ctypes.c_int64, "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
+    restype = {"mh_plan": ctypes.c_int64, "mh_multi_plan": ctypes.c_int64, "mh_batch_plan": ctypes.c_int64, "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
                "mh_sched_destroy": None, "mh_server_destroy": None}
     for name in EXPORTS:

@@ -99,6 +99,37 @@ int mh_search_multi(const int *devs, int ndev, const uint8_t *msg, size_t len, u
 int mh_hash_batch(int dev, const uint8_t *msg, size_t len, const uint64_t *nonces, size_t n,
                   uint64_t *out_hashes);
 
+/* ---- batched search: many small Requests in one fused GPU pass ---------- */
+
+/* One Request (message.go:27-34) and its Result.  msg is read during the call only. */
+typedef struct mh_request {
+    const uint8_t *msg;
+    size_t len;
+    uint64_t lower, upper;
+} mh_request;
+
+typedef struct mh_result {
+    int32_t status, reserved; /* MH_OK, or the MH_E* of this request alone */
+    uint64_t hash, nonce;     /* valid when status == MH_OK */
+} mh_result;
+
+/* out[i] = what mh_search(dev, reqs[i].msg, reqs[i].len, reqs[i].lower, reqs[i].upper) returns,
+ * for n Requests at once.  A single small search is almost all fixed cost (reset, launch, merge,
+ * 16-byte copy-back, host synchronise); here every request whose plan holds only generic pieces
+ * (for "cmu440", ranges up to [0, 2 * 10^6]) is fused: its nonces become 2,560-nonce tiles of
+ * one launch of the batch_scan kernel per pass, one segmented merge and one copy-back per pass,
+ * and one host synchronise for the whole call while the passes' results fit the results buffer
+ * (65,536 requests).  A pass holds up to 4,096 requests and 2^18 tiles (MINEHIP_BATCH_SLOTS
+ * lowers the tiles, for tests); a request never spans passes.  A request with a fast piece, or
+ * with more tiles than a pass holds, runs through the mh_search path after the fused passes
+ * (fallback).  Results are in request order either way.
+ * Per-request failures go to out[i].status and do not stop the others: MH_ERANGE (lower > upper),
+ * MH_ETOOLONG, MH_EINVAL (msg NULL with len > 0).  The call returns MH_OK when every request
+ * has a status; n == 0 returns MH_OK without touching a device; NULL arrays with n > 0 return
+ * MH_EINVAL; a device-level failure (MH_ENODEV, MH_EHIP, MH_EINTERNAL) is the call's return
+ * code and leaves out undefined.  One device only. */
+int mh_search_batch(int dev, const mh_request *reqs, size_t n, mh_result *out);
+
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
 
@@ -135,6 +166,18 @@ int mh_msg_decode(const char *json, size_t len, mh_message *out, uint8_t *data, 
  * server's lost-miner path hands the chunk to another miner. */
 int mh_miner_handle(const int *devs, int ndev, const char *request, size_t len, char *out, size_t cap,
                     size_t *out_len);
+
+/* The same step for n payloads a miner holds at once (its connection's queue): status[i], the
+ * bytes at out + i * cap_each and out_lens[i] are what mh_miner_handle would give for
+ * requests[i] (lens[i] bytes) with a buffer of cap_each bytes, MH_ENOTREQ and MH_ERANGE
+ * included.  The valid Requests that mh_search_batch fuses go through one mh_search_batch on
+ * devs[0]; the others (fallbacks) through mh_miner_handle's own path, over all listed devices.
+ * Returns MH_OK when every payload has a status (MH_OK: answer with the Result; MH_ENOTREQ,
+ * MH_ERANGE: skip; MH_EINVAL: cap_each is short, out_lens[i] is the size needed); a device-level
+ * failure of a search (MH_ENODEV, MH_EHIP, MH_EINTERNAL) is the call's return code: the miner
+ * should exit.  out_lens may be NULL. */
+int mh_miner_handle_batch(const int *devs, int ndev, const char *const *requests, const size_t *lens, size_t n,
+                          char *out, size_t cap_each, size_t *out_lens, int *status);
 
 /* ---- measurement (no reference counterpart; used by bench.py) ---------- */
 
@@ -198,6 +241,25 @@ typedef struct mh_piece {
  * or cap + 1 when the plan has more than cap pieces (the first cap written),
  * or a negative MH_E* code. */
 int64_t mh_plan(const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper, mh_piece *out, int64_t cap);
+
+/* One item of a batch plan: an entry (one generic piece) of a fused request, or a fallback
+ * request. */
+typedef struct mh_batch_item {
+    uint64_t req;          /* index into reqs */
+    uint64_t first, count; /* fused: the entry's nonces; fallback: the request's (count mod 2^64) */
+    int32_t kind;          /* 0 fused, 1 fallback */
+    int32_t pass;          /* fused: its pass, from 0; fallback: -1 */
+    uint32_t slot, slots;  /* fused: first partial slot within the pass, and tiles: the aligned
+                              decades first/10 .. (first+count-1)/10 in tiles of 256 decades
+                              (2,560 nonces); fallback: 0, 0 */
+} mh_batch_item;
+
+/* Host only: how mh_search_batch would run reqs[0..n): one item per entry of a fused request and
+ * one item (slots = 0) per fallback request, in request order.  Within a pass the fused requests'
+ * slot segments are contiguous, disjoint and in order.  Returns the item count, cap + 1 when there
+ * are more than cap (the first cap written, as mh_plan), or the MH_E* of the first request
+ * mh_search would refuse.  n == 0 returns 0. */
+int64_t mh_batch_plan(const mh_request *reqs, size_t n, mh_batch_item *out, int64_t cap);
 
 /* One span of mh_search_multi's adaptive split (chunk == 0), ABI 4. */
 typedef struct mh_span {
