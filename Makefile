@@ -21,6 +21,10 @@ ADD3_SPLIT ?= 3
 FAST_CO := $(BUILD)/fast_search.hsaco
 FAST_O  := $(BUILD)/fast_co.o
 FASTFLAGS ?=
+# the code objects built from fast_search.hip, every one through the same passes: the product's
+# (embedded in the library) and the coarse-hash test variant (-DMH_HASH_KEEP)
+FAST_NAMES := fast_search fast_search_keep
+FASTFLAGS_fast_search_keep := -DMH_HASH_KEEP
 
 LSPLIB  := $(PKG)/minehip/liblsp440.so
 APPS    := $(CSRC)/apps
@@ -30,7 +34,8 @@ RPATH   := -Wl,-rpath,'$$ORIGIN/../minehip'
 
 DEVLIB  := $(BUILD)/dev/libminehip.so
 
-all: $(LIB) $(LSPLIB) $(CLIS) oracle dev $(BUILD)/libclockprobe.so $(BUILD)/libvaluenergy.so $(FAST_MIX) $(BUILD)/fast_search_nomarker.hsaco
+all: $(LIB) $(LSPLIB) $(CLIS) oracle dev $(BUILD)/libclockprobe.so $(BUILD)/libvaluenergy.so $(FAST_MIX) $(BUILD)/fast_search_nomarker.hsaco \
+     $(BUILD)/fast_search_keep.hsaco
 
 # LSP endpoint (host only, wire compatible with the reference's Go lsp package)
 $(LSPLIB): $(CSRC)/lsp/lsp.cpp include/lsp440.h
@@ -40,8 +45,10 @@ $(LIB): $(SRCS) $(HDRS) $(FAST_O)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -x none $(FAST_O)
 
 # dev build: the same library plus the experiment / test hooks (MINEHIP_DEV_CODE_OBJECT,
-# MINEHIP_DEV_LDS, MINEHIP_TEST_FAIL_WORKER, MINEHIP_TEST_SPAWN_LIMIT).  Never the package's library: tools and the
-# tests that need a hook load it explicitly (MINEHIP_LIB=build/dev/libminehip.so).
+# MINEHIP_DEV_LDS, MINEHIP_TEST_FAIL_WORKER, MINEHIP_TEST_SPAWN_LIMIT, and MINEHIP_DEV_HASH_KEEP=k0,k1: every hash
+# cut to its top k0 + k1 bits so that nonces tie, with build/fast_search_keep.hsaco as the fast code object,
+# tests/test_gpu_ties.py).  Never the package's library: tools and the tests that need a hook load it
+# explicitly (MINEHIP_LIB=build/dev/libminehip.so).
 dev: $(DEVLIB)
 $(DEVLIB): $(SRCS) $(HDRS) $(FAST_O)
 	mkdir -p $(BUILD)/dev
@@ -50,9 +57,10 @@ $(DEVLIB): $(SRCS) $(HDRS) $(FAST_O)
 # fast_search<J, MODE>: gfx950 assembly -> add3 split (every third v_add3 as two full-rate adds)
 # -> issue-priority pass (s_setprio around half-/full-rate runs) -> code object ->
 # embedded in the library (fast_co.S); the per-nonce loops' issued mix -> fast_loop_mix.json (bench)
-$(FAST_S): $(CSRC)/fast_search.hip $(FAST_HDRS)
+# ($* is the code object's name, one of FAST_NAMES; the product's files are FAST_S, FAST_SP, FAST_PS, FAST_CO)
+$(FAST_NAMES:%=$(BUILD)/%.s): $(BUILD)/%.s: $(CSRC)/fast_search.hip $(FAST_HDRS)
 	mkdir -p $(BUILD)
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) $(FASTFLAGS) --cuda-device-only -S -o $@ $<
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) $(FASTFLAGS) $(FASTFLAGS_$*) --cuda-device-only -S -o $@ $<
 # the split factor is a prerequisite: `make ADD3_SPLIT=k` after a build redoes the split (and the
 # loop mix bench.py reads) instead of reusing the old assembly
 ADD3_STAMP := $(BUILD)/add3_split.$(ADD3_SPLIT).stamp
@@ -60,15 +68,15 @@ $(ADD3_STAMP):
 	mkdir -p $(BUILD)
 	rm -f $(BUILD)/add3_split.*.stamp
 	touch $@
-$(FAST_SP): $(FAST_S) $(CSRC)/add3_split.py $(ADD3_STAMP)
+$(FAST_NAMES:%=$(BUILD)/%_split.s): $(BUILD)/%_split.s: $(BUILD)/%.s $(CSRC)/add3_split.py $(ADD3_STAMP)
 	python3 $(CSRC)/add3_split.py $(ADD3_SPLIT) $< $@
-$(FAST_PS): $(FAST_SP) $(CSRC)/issue_prio.py $(CSRC)/valu_rates.py
+$(FAST_NAMES:%=$(BUILD)/%_prio.s): $(BUILD)/%_prio.s: $(BUILD)/%_split.s $(CSRC)/issue_prio.py $(CSRC)/valu_rates.py
 	python3 $(CSRC)/issue_prio.py $< $@
 $(FAST_MIX): $(FAST_PS) $(CSRC)/loop_mix.py $(CSRC)/valu_rates.py
 	python3 $(CSRC)/loop_mix.py $< $@
-$(FAST_CO): $(FAST_PS)
-	$(LLVM)/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=$(ARCH) -c -o $(BUILD)/fast_search_prio.o $<
-	$(LLVM)/ld.lld -shared -o $@ $(BUILD)/fast_search_prio.o
+$(FAST_NAMES:%=$(BUILD)/%.hsaco): $(BUILD)/%.hsaco: $(BUILD)/%_prio.s
+	$(LLVM)/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=$(ARCH) -c -o $(BUILD)/$*_prio.o $<
+	$(LLVM)/ld.lld -shared -o $@ $(BUILD)/$*_prio.o
 # test artefact: the same kernels without the work-queue marker (mh_fast_queue_args), as a code
 # object built from older sources would be; the dev build must run it one workgroup per chunk
 # (tests/test_gpu_parity.py::test_code_object_without_queue_marker_runs_static)
@@ -126,8 +134,9 @@ build/valu_%: tools/valu_%.hip
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $<
 
 clean:
-	rm -f $(LIB) $(DEVLIB) $(LSPLIB) $(CLIS) $(FAST_S) $(FAST_SP) $(FAST_PS) $(FAST_MIX) $(FAST_CO) $(FAST_O) \
-	      $(BUILD)/fast_search_prio.o $(BUILD)/libclockprobe.so $(BUILD)/libvaluenergy.so $(BUILD)/add3_split.*.stamp \
+	rm -f $(LIB) $(DEVLIB) $(LSPLIB) $(CLIS) $(FAST_MIX) $(FAST_O) \
+	      $(foreach n,$(FAST_NAMES),$(BUILD)/$(n).s $(BUILD)/$(n)_split.s $(BUILD)/$(n)_prio.s $(BUILD)/$(n)_prio.o $(BUILD)/$(n).hsaco) \
+	      $(BUILD)/libclockprobe.so $(BUILD)/libvaluenergy.so $(BUILD)/add3_split.*.stamp \
 	      $(BUILD)/fast_search_nomarker.*
 	$(MAKE) -s -C oracle clean
 

@@ -15,7 +15,9 @@
 // half-rate VALU ops, 0 before every run of full-rate ones),
 // assembled into a code object and embedded in libminehip.so (fast_co.S),
 // which loads it per device (search_kernels.hip, fast_module).  It is never
-// part of the library's fat binary.
+// part of the library's fat binary.  -DMH_HASH_KEEP builds the coarse-hash test variant
+// (build/fast_search_keep.hsaco, through the same passes), which only the dev
+// build's MINEHIP_DEV_CODE_OBJECT hook ever loads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -252,6 +254,11 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
     const uint64_t wave_u0 = a.u_start + (uint64_t)blk * kBlockThreads + wave * 64u;
     uint32_t wbh0 = 0xFFFFFFFFu, wbh1 = 0xFFFFFFFFu;
     uint64_t wbn = ~0ull;
+#ifdef MH_HASH_KEEP
+    // coarse-hash variant (build/fast_search_keep.hsaco, layout.hpp keep_word): the bits of H0 and
+    // H1 that enter the comparisons below; the comparisons themselves are the product's
+    const uint32_t keep0 = keep_mask0(a.pad_), keep1 = keep_mask1(a.pad_);
+#endif
 
     for (uint32_t g = 0; g < a.n_groups; ++g) {
         // ---- per group of 10 nonces --------------------------------------
@@ -349,11 +356,18 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 sha256_block_kw_last(s2, a.kw1, h0, a63);  // block 1: padding + length only
                 a63 += s2[1] - st[1];                       // so that H1 = st[1] + a63 below
             }
+#ifdef MH_HASH_KEEP
+            h0 &= keep0;
+#endif
             // New wave best (rare): a uniform branch, so H1 and the
             // lexicographic compare cost nothing on the common path.
             uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= wbh0) & valid_mask;
             if (__builtin_expect(cm != 0ull, 0)) {
+#ifdef MH_HASH_KEEP
+                const uint32_t h1 = (st[1] + a63) & keep1;
+#else
                 const uint32_t h1 = st[1] + a63;
+#endif
                 const uint32_t q = g * 10u + i;
                 // Many candidates (the first nonce of a run makes every lane one): keep only
                 // the lanes holding their smallest H0, found by a DPP wave-min, instead of a
@@ -433,6 +447,12 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void fast_search
 // older sources runs one workgroup per chunk instead of searching only its first chunks.
 extern "C" {
 __device__ __attribute__((used)) uint8_t mh_fast_queue_args[sizeof(FastArgs)];
+#ifdef MH_HASH_KEEP
+// Marker of the coarse-hash variant: its kernels mask (H0, H1) by FastArgs::pad_.  The dev build
+// runs a search with MINEHIP_DEV_HASH_KEEP set only on a code object that carries it, so masked
+// generic pieces never meet unmasked fast pieces (search_kernels.hip, fast_keep_ok).
+__device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
+#endif
 }
 
 // The instantiations the planner uses (plan.cpp; launch by mangled name in

@@ -71,6 +71,18 @@ constexpr bool fast_kernel_exists(int J, int mode) {
 }
 constexpr uint32_t kNoHole = 20;  // a digit index no layout reaches (d <= 20)
 
+// Coarse-hash word of the dev build (MINEHIP_DEV_HASH_KEEP=k0,k1): a test hook that
+// makes many nonces share a hash, so the (hash, nonce) tie-breaking of every kernel and merge runs
+// on the GPU.  It travels in the padding words FastArgs::pad_ and GenArgs::pad: 0 is off (all the
+// product library ever passes); otherwise kKeepFlag | k0 << 8 | k1, and a scan kernel built with
+// the hook replaces each nonce's (H0, H1) by (H0 & keep_mask(k0), H1 & keep_mask(k1)), the top
+// k0 / k1 bits, before any comparison.
+constexpr uint32_t kKeepFlag = 1u << 31;
+constexpr uint32_t keep_word(uint32_t k0, uint32_t k1) { return kKeepFlag | (k0 << 8) | k1; }
+constexpr uint32_t keep_mask(uint32_t k) { return k ? ~0u << (32u - k) : 0u; }  // k = 0..32
+constexpr uint32_t keep_mask0(uint32_t word) { return word ? keep_mask((word >> 8) & 63u) : ~0u; }
+constexpr uint32_t keep_mask1(uint32_t word) { return word ? keep_mask(word & 63u) : ~0u; }
+
 // Arguments of the fast (run) kernel.  Passed by value: lands in SGPRs.
 struct FastArgs {
     uint32_t mid[8];      // chaining state before tail block 0
@@ -96,7 +108,7 @@ struct FastArgs {
     uint32_t g_last;
     uint32_t g_hole;
     uint32_t hole_w;
-    uint32_t pad_;
+    uint32_t pad_;        // 0; dev build: the coarse-hash word (keep_word above)
     uint64_t u_mul;
     uint64_t g_mul;
     uint64_t i_mul;
@@ -116,7 +128,7 @@ struct GenArgs {
     uint64_t first;       // scan: first nonce
     uint64_t count;       // scan: nonces in this launch
     uint32_t t;           // tail prefix length, 0..63
-    uint32_t pad;
+    uint32_t pad;         // 0; dev build: the coarse-hash word (keep_word above)
 };
 
 // ---- batched search (batch_scan / merge_segments) ----

@@ -7,6 +7,7 @@
 // result back.  No CPU fallback exists: without a gfx950 device the calls fail
 // with MH_ENODEV.
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -32,6 +33,9 @@
 
 namespace mh {
 hipError_t fast_module_init(int dev);
+#ifdef MH_DEV_HOOKS
+hipError_t fast_keep_ok(int dev, bool* ok);
+#endif
 hipError_t launch_fast(int dev, int J, int mode, const FastArgs& a, Partial* partials, hipStream_t s);
 hipError_t launch_generic_scan(const GenArgs& a, Partial* partials, uint32_t blocks, hipStream_t s);
 hipError_t launch_hash_batch(const GenArgs& a, const uint64_t* d_nonces, uint64_t* d_out, uint64_t n,
@@ -109,6 +113,10 @@ struct DevCtx {
     uint8_t* h_btab = nullptr;  // pinned staging of the same bytes
     Partial* d_bres = nullptr;  // one result per request of the passes in flight
     Partial* h_bres = nullptr;  // pinned
+#ifdef MH_DEV_HOOKS
+    uint32_t keep = 0;        // this call's coarse-hash word (MINEHIP_DEV_HASH_KEEP; 0: unset)
+    bool keep_fast = false;   // ... and the fast code object in use is the variant that reads it
+#endif
     // profiling
     bool prof = false;
     std::vector<Timed> pool;
@@ -178,6 +186,29 @@ int init_locked(DevCtx* c, int dev) {
     c->ready = true;
     return MH_OK;
 }
+
+#ifdef MH_DEV_HOOKS
+// MINEHIP_DEV_HASH_KEEP=k0,k1 (dev build only, 0 <= k <= 32): every scan kernel keeps
+// only the top k0 bits of H0 and the top k1 bits of H1 of each nonce's hash, so that many nonces
+// tie and the (hash, nonce) tie-breaking of the kernels and merges decides the result; the search
+// returns the masked hash.  Read by every search (one process can run many settings) into
+// c->keep, the word the pieces carry (layout.hpp keep_word).  The fast kernels mask only in the
+// variant code object (build/fast_search_keep.hsaco through MINEHIP_DEV_CODE_OBJECT): with any
+// other, a fast piece fails the search (enqueue_piece) instead of mixing masked and full hashes.
+int read_hash_keep(DevCtx* c) {
+    c->keep = 0;
+    c->keep_fast = false;
+    const char* e = getenv("MINEHIP_DEV_HASH_KEEP");
+    if (!e || !*e) return MH_OK;
+    unsigned k0 = 0, k1 = 0;
+    char rest = 0;
+    if (sscanf(e, "%u,%u%c", &k0, &k1, &rest) != 2 || k0 > 32u || k1 > 32u)
+        return fail(MH_EINVAL, "MINEHIP_DEV_HASH_KEEP: expected k0,k1 with 0 <= k <= 32");
+    MH_HIP(mh::fast_keep_ok(c->dev, &c->keep_fast));
+    c->keep = mh::keep_word(k0, k1);
+    return MH_OK;
+}
+#endif
 
 // Stream must be idle or synchronised by the caller.
 int harvest_locked(DevCtx* c) {
@@ -262,6 +293,18 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
     Partial* out = c->d_partials + c->poff;
     Timed* tm = nullptr;
     mh::FastArgs fa = p.fa;
+#ifdef MH_DEV_HOOKS
+    mh::GenArgs ga = p.ga;
+    ga.pad = c->keep;
+    if (p.kind == 0) {
+        if (c->keep && !c->keep_fast)
+            return fail(MH_EINVAL, "MINEHIP_DEV_HASH_KEEP is set but the fast code object is not the coarse-hash "
+                                   "variant (MINEHIP_DEV_CODE_OBJECT=build/fast_search_keep.hsaco)");
+        fa.pad_ = c->keep;
+    }
+#else
+    const mh::GenArgs& ga = p.ga;
+#endif
     if (p.kind == 0) {
         fa.n_chunks = blocks;
         // work queue while this search has counters left (a longer search runs the rest static)
@@ -282,7 +325,7 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
     if (p.kind == 0)
         MH_HIP(mh::launch_fast(c->dev, p.J, p.mode, fa, out, s));
     else
-        MH_HIP(mh::launch_generic_scan(p.ga, out, blocks, s));
+        MH_HIP(mh::launch_generic_scan(ga, out, blocks, s));
     if (tm) MH_HIP(hipEventRecord(tm->stop, s));
     c->poff += blocks;
     if (c->prof) {
@@ -369,6 +412,10 @@ int search_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, 
     if (rc) return rc;
     const uint64_t t0 = now_ns();
     MH_HIP(hipSetDevice(dev));
+#ifdef MH_DEV_HOOKS
+    rc = read_hash_keep(c);
+    if (rc) return rc;
+#endif
     MH_HIP(hipMemsetAsync(c->d_best, 0xFF, sizeof(Partial), c->stream));
     const mh::PlanOpts opt = plan_opts();
     if (opt.queue) MH_HIP(hipMemsetAsync(c->d_counters, 0, sizeof(uint32_t) * kQueueSlots, c->stream));
@@ -483,6 +530,9 @@ int batch_run_pass(DevCtx* c, const mh::BatchRequest* reqs, const mh::BatchTable
     uint8_t* h = c->h_btab + pend->toff;
     uint8_t* d = c->d_btab + pend->toff;
     memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+#ifdef MH_DEV_HOOKS
+    for (size_t i = 0; i < ne; ++i) ((mh::BatchEntry*)h)[i].g.pad = c->keep;
+#endif
     memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
     memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
     MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
@@ -520,6 +570,10 @@ int batch_run_fused(int dev, const mh::BatchRequest* reqs, const std::vector<mh:
     MH_HIP(hipSetDevice(dev));
     rc = batch_init_locked(c);
     if (rc) return rc;
+#ifdef MH_DEV_HOOKS
+    rc = read_hash_keep(c);
+    if (rc) return rc;
+#endif
     BatchPending pend;
     mh::BatchTables t;
     for (int p = 0; p < passes && !rc; ++p) {

@@ -99,6 +99,10 @@ __global__ __launch_bounds__(kBlockThreads) void generic_scan(const GenArgs a, P
     const uint64_t n = a.first + gid;
     uint32_t h0, h1;
     hash_generic(a, n, h0, h1);
+#ifdef MH_DEV_HOOKS  // coarse-hash test hook (layout.hpp keep_word): a.pad = 0, all bits, unless set
+    h0 &= keep_mask0(a.pad);
+    h1 &= keep_mask1(a.pad);
+#endif
     uint64_t hash = ((uint64_t)h0 << 32) | h1, nonce = n;
     if (gid >= a.count) {
         hash = ~0ull;
@@ -237,6 +241,10 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
         }
         uint32_t h0, h1;
         sha256_block_h01(s, x, h0, h1);
+#ifdef MH_DEV_HOOKS  // coarse-hash test hook, as in generic_scan
+        h0 &= keep_mask0(a.pad);
+        h1 &= keep_mask1(a.pad);
+#endif
         const uint64_t hash = ((uint64_t)h0 << 32) | h1, n = n0 + j;
         if (lex_less(hash, n, bh, bn)) {
             bh = hash;
@@ -314,6 +322,9 @@ std::mutex g_mod_mu;
 std::map<std::pair<std::string, int>, hipModule_t> g_mods;                    // (file or "", dev)
 std::map<std::pair<hipModule_t, int>, hipFunction_t> g_funcs;                // (module, J + 16 * mode)
 std::map<hipModule_t, bool> g_queue_ok;  // the module's kernels run the work-queue loop (marker)
+#ifdef MH_DEV_HOOKS
+std::map<hipModule_t, bool> g_keep_ok;   // the module's kernels mask hashes by FastArgs::pad_ (marker)
+#endif
 
 // queue_ok: the code object carries fast_search.hip's mh_fast_queue_args marker at this
 // library's sizeof(FastArgs), i.e. its kernels claim chunks from a.counter
@@ -340,6 +351,12 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                             gsz == sizeof(FastArgs);
         (void)hipGetLastError();
         g_queue_ok[m] = marked;
+#ifdef MH_DEV_HOOKS
+        const bool keeps = hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_hash_keep") == hipSuccess &&
+                           gsz == sizeof(FastArgs);
+        (void)hipGetLastError();
+        g_keep_ok[m] = keeps;
+#endif
     }
     if (queue_ok) *queue_ok = g_queue_ok[it->second];
     auto fit = g_funcs.find({it->second, J + 16 * mode});
@@ -367,6 +384,22 @@ hipError_t fast_module_init(int dev) {
     hipFunction_t f;
     return fast_function(dev, 4, kModeOne, &f);
 }
+
+#ifdef MH_DEV_HOOKS
+// Whether the fast code object in use on dev (MINEHIP_DEV_CODE_OBJECT, or the embedded one) is the
+// coarse-hash variant (fast_search.hip, mh_fast_hash_keep): only such kernels read FastArgs::pad_.
+hipError_t fast_keep_ok(int dev, bool* ok) {
+    hipFunction_t f;
+    *ok = false;
+    const hipError_t e = fast_function(dev, 4, kModeOne, &f);  // loads the code object if need be
+    if (e != hipSuccess) return e;
+    const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
+    std::lock_guard<std::mutex> g(g_mod_mu);
+    const auto it = g_mods.find({(co && *co) ? co : "", dev});
+    if (it != g_mods.end()) *ok = g_keep_ok[it->second];
+    return hipSuccess;
+}
+#endif
 
 // Workgroups of f that fit on dev at once (occupancy x CUs), cached per function.
 hipError_t resident_groups(int dev, hipFunction_t f, unsigned lds, uint32_t* out) {
