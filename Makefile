@@ -47,7 +47,8 @@ $(LIB): $(SRCS) $(HDRS) $(FAST_O)
 # dev build: the same library plus the experiment / test hooks (MINEHIP_DEV_CODE_OBJECT,
 # MINEHIP_DEV_LDS, MINEHIP_TEST_FAIL_WORKER, MINEHIP_TEST_SPAWN_LIMIT, and MINEHIP_DEV_HASH_KEEP=k0,k1: every hash
 # cut to its top k0 + k1 bits so that nonces tie, with build/fast_search_keep.hsaco as the fast code object,
-# tests/test_gpu_ties.py).  Never the package's library: tools and the tests that need a hook load it
+# tests/test_gpu_ties.py; MINEHIP_DEV_HASH_XOR=<hex>: every hash XORed with a 64-bit constant before that cut, so
+# that a test chooses the winning nonce, with the same code object, tests/test_gpu_probe.py).  Never the package's library: tools and the tests that need a hook load it
 # explicitly (MINEHIP_LIB=build/dev/libminehip.so).
 dev: $(DEVLIB)
 $(DEVLIB): $(SRCS) $(HDRS) $(FAST_O)

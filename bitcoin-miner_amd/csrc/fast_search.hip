@@ -149,6 +149,16 @@ __device__ __forceinline__ uint64_t spread(uint64_t x, uint32_t k, uint32_t w) {
     return x * p + lo;
 }
 
+#ifdef MH_HASH_KEEP
+// Hash-XOR word of the test variant (MINEHIP_DEV_HASH_XOR, layout.hpp): {high, low} 32 bits of the
+// constant every nonce's (H0, H1) is XORed with before the keep mask; zero (off) unless the dev
+// build writes it before a search (search_kernels.hip, set_hash_xor).  Its presence also marks the
+// code object as one whose kernels apply it.
+extern "C" {
+__device__ __attribute__((used)) uint32_t mh_dev_hash_xor[2];
+}
+#endif
+
 // One workgroup-sized chunk: the 256 runs u_start + 256 * blk + threadIdx.x, their minimum
 // written to partials[blk].
 // MODE % 3 is the tail layout (One, Pre, Two); MODE >= 3 (Early): the per-nonce digit ends word
@@ -258,6 +268,7 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
     // coarse-hash variant (build/fast_search_keep.hsaco, layout.hpp keep_word): the bits of H0 and
     // H1 that enter the comparisons below; the comparisons themselves are the product's
     const uint32_t keep0 = keep_mask0(a.pad_), keep1 = keep_mask1(a.pad_);
+    const uint32_t xor0 = mh_dev_hash_xor[0], xor1 = mh_dev_hash_xor[1];  // the hash-XOR hook, before the mask
 #endif
 
     for (uint32_t g = 0; g < a.n_groups; ++g) {
@@ -357,14 +368,14 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 a63 += s2[1] - st[1];                       // so that H1 = st[1] + a63 below
             }
 #ifdef MH_HASH_KEEP
-            h0 &= keep0;
+            h0 = (h0 ^ xor0) & keep0;
 #endif
             // New wave best (rare): a uniform branch, so H1 and the
             // lexicographic compare cost nothing on the common path.
             uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= wbh0) & valid_mask;
             if (__builtin_expect(cm != 0ull, 0)) {
 #ifdef MH_HASH_KEEP
-                const uint32_t h1 = (st[1] + a63) & keep1;
+                const uint32_t h1 = ((st[1] + a63) ^ xor1) & keep1;
 #else
                 const uint32_t h1 = st[1] + a63;
 #endif

@@ -82,6 +82,12 @@ constexpr uint32_t keep_word(uint32_t k0, uint32_t k1) { return kKeepFlag | (k0 
 constexpr uint32_t keep_mask(uint32_t k) { return k ? ~0u << (32u - k) : 0u; }  // k = 0..32
 constexpr uint32_t keep_mask0(uint32_t word) { return word ? keep_mask((word >> 8) & 63u) : ~0u; }
 constexpr uint32_t keep_mask1(uint32_t word) { return word ? keep_mask(word & 63u) : ~0u; }
+// Hash-XOR constant of the dev build (MINEHIP_DEV_HASH_XOR=<1-16 hex digits>): a scan
+// kernel built with the hook XORs each nonce's (H0, H1) with the constant's high and low 32 bits
+// before the keep mask above, so a test chooses which nonce wins (x = Hash(msg, n): the search must
+// return (0, n)).  The padding words are the keep word's, so it travels in no argument struct but
+// in a device word mh_dev_hash_xor[2] = {high, low}, zero (off) unless the dev build writes it: one
+// in the dev library (search_kernels.hip), one in the variant fast code object (fast_search.hip).
 
 // Arguments of the fast (run) kernel.  Passed by value: lands in SGPRs.
 struct FastArgs {

@@ -35,6 +35,7 @@ namespace mh {
 hipError_t fast_module_init(int dev);
 #ifdef MH_DEV_HOOKS
 hipError_t fast_keep_ok(int dev, bool* ok);
+hipError_t set_hash_xor(int dev, uint64_t x, hipStream_t s, bool* fast_ok);
 #endif
 hipError_t launch_fast(int dev, int J, int mode, const FastArgs& a, Partial* partials, hipStream_t s);
 hipError_t launch_generic_scan(const GenArgs& a, Partial* partials, uint32_t blocks, hipStream_t s);
@@ -116,6 +117,8 @@ struct DevCtx {
 #ifdef MH_DEV_HOOKS
     uint32_t keep = 0;        // this call's coarse-hash word (MINEHIP_DEV_HASH_KEEP; 0: unset)
     bool keep_fast = false;   // ... and the fast code object in use is the variant that reads it
+    bool xor_on = false;      // this call XORs every hash with a constant (MINEHIP_DEV_HASH_XOR, non-zero)
+    bool xor_fast = false;    // ... and the fast code object in use has the word its kernels read it from
 #endif
     // profiling
     bool prof = false;
@@ -206,6 +209,33 @@ int read_hash_keep(DevCtx* c) {
         return fail(MH_EINVAL, "MINEHIP_DEV_HASH_KEEP: expected k0,k1 with 0 <= k <= 32");
     MH_HIP(mh::fast_keep_ok(c->dev, &c->keep_fast));
     c->keep = mh::keep_word(k0, k1);
+    return MH_OK;
+}
+
+// MINEHIP_DEV_HASH_XOR=<1-16 hex digits> (dev build only): every scan kernel XORs each
+// nonce's (H0, H1) with the high and low 32 bits of the constant before the keep mask and before any
+// comparison, so a test decides which nonce of a range wins: with x = Hash(msg, n) the search returns
+// (0, n) exactly if it hashes n correctly, considers it and rebuilds its value.  Unset or zero: off.
+// Read by every search, after read_hash_keep and before anything of the search is enqueued; the
+// constant reaches the kernels through a device word (search_kernels.hip set_hash_xor) rewritten only
+// when the value changes.  The fast kernels XOR only in the variant code object: with any other,
+// a fast piece fails the search (enqueue_piece).
+int read_hash_xor(DevCtx* c) {
+    c->xor_on = c->xor_fast = false;
+    const char* e = getenv("MINEHIP_DEV_HASH_XOR");
+    uint64_t x = 0;
+    if (e && *e) {
+        size_t n = 0;
+        for (; e[n]; ++n) {
+            const char ch = e[n];
+            const int v = (ch >= '0' && ch <= '9') ? ch - '0' : (ch >= 'a' && ch <= 'f') ? ch - 'a' + 10
+                        : (ch >= 'A' && ch <= 'F') ? ch - 'A' + 10 : -1;
+            if (v < 0 || n >= 16) return fail(MH_EINVAL, "MINEHIP_DEV_HASH_XOR: expected 1 to 16 hex digits");
+            x = (x << 4) | (uint64_t)v;
+        }
+    }
+    MH_HIP(mh::set_hash_xor(c->dev, x, c->stream, &c->xor_fast));
+    c->xor_on = x != 0;
     return MH_OK;
 }
 #endif
@@ -300,6 +330,9 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
         if (c->keep && !c->keep_fast)
             return fail(MH_EINVAL, "MINEHIP_DEV_HASH_KEEP is set but the fast code object is not the coarse-hash "
                                    "variant (MINEHIP_DEV_CODE_OBJECT=build/fast_search_keep.hsaco)");
+        if (c->xor_on && !c->xor_fast)
+            return fail(MH_EINVAL, "MINEHIP_DEV_HASH_XOR is set but the fast code object has no mh_dev_hash_xor "
+                                   "(MINEHIP_DEV_CODE_OBJECT=build/fast_search_keep.hsaco)");
         fa.pad_ = c->keep;
     }
 #else
@@ -414,6 +447,8 @@ int search_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, 
     MH_HIP(hipSetDevice(dev));
 #ifdef MH_DEV_HOOKS
     rc = read_hash_keep(c);
+    if (rc) return rc;
+    rc = read_hash_xor(c);
     if (rc) return rc;
 #endif
     MH_HIP(hipMemsetAsync(c->d_best, 0xFF, sizeof(Partial), c->stream));
@@ -572,6 +607,8 @@ int batch_run_fused(int dev, const mh::BatchRequest* reqs, const std::vector<mh:
     if (rc) return rc;
 #ifdef MH_DEV_HOOKS
     rc = read_hash_keep(c);
+    if (rc) return rc;
+    rc = read_hash_xor(c);
     if (rc) return rc;
 #endif
     BatchPending pend;

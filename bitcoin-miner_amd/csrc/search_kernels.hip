@@ -42,6 +42,12 @@
 extern "C" const unsigned char mh_fast_co_begin[];
 
 namespace mh {
+#ifdef MH_DEV_HOOKS
+// Hash-XOR test hook (MINEHIP_DEV_HASH_XOR, layout.hpp): {high, low} 32 bits of the constant the
+// scan kernels of this library XOR every nonce's (H0, H1) with before the keep mask; zero (off)
+// unless set_hash_xor below writes it before a search.
+__device__ uint32_t mh_dev_hash_xor[2];
+#endif
 namespace dev {
 
 // Generic Hash(msg, n): formats n in registers and hashes the 1 or 2 tail
@@ -99,9 +105,9 @@ __global__ __launch_bounds__(kBlockThreads) void generic_scan(const GenArgs a, P
     const uint64_t n = a.first + gid;
     uint32_t h0, h1;
     hash_generic(a, n, h0, h1);
-#ifdef MH_DEV_HOOKS  // coarse-hash test hook (layout.hpp keep_word): a.pad = 0, all bits, unless set
-    h0 &= keep_mask0(a.pad);
-    h1 &= keep_mask1(a.pad);
+#ifdef MH_DEV_HOOKS  // hash-XOR, then coarse-hash test hook (layout.hpp keep_word): a.pad = 0, all bits, unless set
+    h0 = (h0 ^ mh_dev_hash_xor[0]) & keep_mask0(a.pad);
+    h1 = (h1 ^ mh_dev_hash_xor[1]) & keep_mask1(a.pad);
 #endif
     uint64_t hash = ((uint64_t)h0 << 32) | h1, nonce = n;
     if (gid >= a.count) {
@@ -241,9 +247,9 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
         }
         uint32_t h0, h1;
         sha256_block_h01(s, x, h0, h1);
-#ifdef MH_DEV_HOOKS  // coarse-hash test hook, as in generic_scan
-        h0 &= keep_mask0(a.pad);
-        h1 &= keep_mask1(a.pad);
+#ifdef MH_DEV_HOOKS  // hash-XOR and coarse-hash test hooks, as in generic_scan
+        h0 = (h0 ^ mh_dev_hash_xor[0]) & keep_mask0(a.pad);
+        h1 = (h1 ^ mh_dev_hash_xor[1]) & keep_mask1(a.pad);
 #endif
         const uint64_t hash = ((uint64_t)h0 << 32) | h1, n = n0 + j;
         if (lex_less(hash, n, bh, bn)) {
@@ -324,6 +330,9 @@ std::map<std::pair<hipModule_t, int>, hipFunction_t> g_funcs;                // 
 std::map<hipModule_t, bool> g_queue_ok;  // the module's kernels run the work-queue loop (marker)
 #ifdef MH_DEV_HOOKS
 std::map<hipModule_t, bool> g_keep_ok;   // the module's kernels mask hashes by FastArgs::pad_ (marker)
+std::map<hipModule_t, hipDeviceptr_t> g_xor_ptr;  // the module's mh_dev_hash_xor (null: its kernels do not XOR)
+std::map<hipModule_t, uint64_t> g_xor_mod;        // ... and the value it holds
+std::map<int, uint64_t> g_xor_lib;                // the value this library's own mh_dev_hash_xor holds, per device
 #endif
 
 // queue_ok: the code object carries fast_search.hip's mh_fast_queue_args marker at this
@@ -356,6 +365,11 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                            gsz == sizeof(FastArgs);
         (void)hipGetLastError();
         g_keep_ok[m] = keeps;
+        const bool xors = hipModuleGetGlobal(&gp, &gsz, m, "mh_dev_hash_xor") == hipSuccess &&
+                          gsz == 2 * sizeof(uint32_t);
+        (void)hipGetLastError();
+        g_xor_ptr[m] = xors ? gp : nullptr;
+        g_xor_mod[m] = 0;
 #endif
     }
     if (queue_ok) *queue_ok = g_queue_ok[it->second];
@@ -397,6 +411,43 @@ hipError_t fast_keep_ok(int dev, bool* ok) {
     std::lock_guard<std::mutex> g(g_mod_mu);
     const auto it = g_mods.find({(co && *co) ? co : "", dev});
     if (it != g_mods.end()) *ok = g_keep_ok[it->second];
+    return hipSuccess;
+}
+
+// Make x the hash-XOR constant (MINEHIP_DEV_HASH_XOR; 0: off) of this library's scan kernels on dev
+// (the current device) and of the fast code object in use there, if that one has the word
+// (*fast_ok).  Each word is rewritten only when its value changes, by a copy on s that has
+// completed on return; the caller holds the device idle.
+hipError_t set_hash_xor(int dev, uint64_t x, hipStream_t s, bool* fast_ok) {
+    hipFunction_t f;
+    *fast_ok = false;
+    hipError_t e = fast_function(dev, 4, kModeOne, &f);  // loads the code object if need be
+    if (e != hipSuccess) return e;
+    const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
+    const uint32_t w[2] = {(uint32_t)(x >> 32), (uint32_t)x};
+    std::lock_guard<std::mutex> g(g_mod_mu);
+    bool wrote = false;
+    if (g_xor_lib[dev] != x) {  // a new key: 0, the words' initial value
+        e = hipMemcpyToSymbolAsync(HIP_SYMBOL(mh_dev_hash_xor), w, sizeof w, 0, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return e;
+        wrote = true;
+    }
+    const auto it = g_mods.find({(co && *co) ? co : "", dev});
+    hipDeviceptr_t gp = it != g_mods.end() ? g_xor_ptr[it->second] : nullptr;
+    if (gp) {
+        *fast_ok = true;
+        if (g_xor_mod[it->second] != x) {
+            e = hipMemcpyHtoDAsync(gp, (void*)w, sizeof w, s);
+            if (e != hipSuccess) return e;
+            wrote = true;
+        }
+    }
+    if (wrote) {
+        e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        g_xor_lib[dev] = x;
+        if (gp) g_xor_mod[it->second] = x;
+    }
     return hipSuccess;
 }
 #endif

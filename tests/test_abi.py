@@ -34,7 +34,8 @@ def test_product_library_has_no_dev_hooks():
     """The experiment and test hooks (code-object override, LDS cap, injected worker failure,
     coarse hashes) exist only in the dev build (`make dev`), never in the package's library (VERDICT r02 #6)."""
     hooks = (b"MINEHIP_DEV_CODE_OBJECT", b"MINEHIP_DEV_LDS", b"MINEHIP_TEST_FAIL_WORKER", b"MINEHIP_TEST_SPAWN_LIMIT",
-             b"MINEHIP_DEV_HASH_KEEP", b"mh_fast_hash_keep")  # the coarse-hash hook and its code object's marker
+             b"MINEHIP_DEV_HASH_KEEP", b"mh_fast_hash_keep",  # the coarse-hash hook and its code object's marker
+             b"MINEHIP_DEV_HASH_XOR", b"mh_dev_hash_xor")     # the hash-XOR hook and its device word
     prod = open(_lib.PRODUCT_LIB_PATH, "rb").read()
     assert not [h for h in hooks if h in prod]
     from conftest import DEV_LIB

@@ -10,6 +10,9 @@ merges of search_multi -- decides which nonce is returned.  The fast kernels mas
 code object build/fast_search_keep.hsaco (the product's source with -DMH_HASH_KEEP, through the
 same passes), loaded through MINEHIP_DEV_CODE_OBJECT.
 
+The reference and the child process also take MINEHIP_DEV_HASH_XOR values (a constant XORed into
+every hash before the mask), default none: tests/test_gpu_probe.py probes single nonces with them.
+
 Reference: masked_min -- the oracle's full hashes of every nonce of the range, masked in numpy;
 the expected result is (min key, first nonce attaining it), bit-exact.  Every GPU test asserts from
 that reference alone that its ties are live: how many nonces attain the minimum and how far apart
@@ -64,13 +67,18 @@ def full_hashes(msg, lo, hi):
     return h
 
 
-def masked_min(msg, lo, hi, k0, k1):
-    """The expected result of a search of [lo, hi] under MINEHIP_DEV_HASH_KEEP=k0,k1: the minimum
-    masked hash, the first nonce attaining it, how many nonces attain it, and the last of them."""
-    key = full_hashes(msg, lo, hi) & np.uint64((keep_mask(k0) << 32) | keep_mask(k1))
-    m = key.min()
-    idx = np.flatnonzero(key == m)
-    return Tie(int(m), lo + int(idx[0]), int(idx.size), lo + int(idx[-1]))
+def masked_min(msg, lo, hi, k0, k1, x=0):
+    """The expected result of a search of [lo, hi] under MINEHIP_DEV_HASH_KEEP=k0,k1 and
+    MINEHIP_DEV_HASH_XOR=x (the XOR first): the minimum key (Hash ^ x) & mask, the first nonce
+    attaining it, how many nonces attain it, and the last of them."""
+    key, mask = full_hashes(msg, lo, hi), (keep_mask(k0) << 32) | keep_mask(k1)
+    if x:
+        key = key ^ np.uint64(x)
+    if mask != U64:
+        key = key & np.uint64(mask)
+    first = int(key.argmin())       # numpy: the first occurrence of the minimum
+    at = key == key[first]
+    return Tie(int(key[first]), lo + first, int(np.count_nonzero(at)), lo + at.size - 1 - int(at[::-1].argmax()))
 
 
 # ---- CPU tests ---------------------------------------------------------------------------------
@@ -93,6 +101,25 @@ def test_masked_min_against_brute_force():
             assert masked_min(msg, lo, hi, k0, k1) == Tie(best[0], best[1], cnt, last), (msg[:8], lo, k0, k1)
         assert masked_min(msg, lo, hi, 0, 0) == Tie(0, lo, 300, hi)
         assert masked_min(msg, lo, hi, 32, 32)[:3] == oracle.search(msg, lo, hi) + (1,)
+        # MINEHIP_DEV_HASH_XOR: x = H(n) of nonces inside the range (positive probes: the reference
+        # is (0, n), attained once) and just outside it (negative ones: a non-zero minimum), and
+        # arbitrary constants, alone and under keep pairs
+        H = lambda n: int.from_bytes(hashlib.sha256(msg + b" " + str(n).encode()).digest()[:8], "big")  # noqa: E731
+        inside = (lo, lo + 1, lo + 137, hi - 1, hi)
+        outside = [n for n in (lo - 1, lo - 2, hi + 1, hi + 2) if 0 <= n <= U64]
+        assert len(outside) >= 2
+        for x in [H(n) for n in inside + tuple(outside)] + [1, U64, 0x8000000000000000, 0x123456789ABCDEF0]:
+            for k0, k1 in ((32, 32), (2, 0), (12, 0), (7, 9)):
+                m0, m1 = (0xFFFFFFFF << (32 - k0)) & 0xFFFFFFFF, (0xFFFFFFFF << (32 - k1)) & 0xFFFFFFFF
+                keys = [(h ^ x) & (m0 << 32 | m1) for h in hs]
+                best = min(keys)
+                at = [n for n, k in zip(range(lo, hi + 1), keys) if k == best]
+                assert masked_min(msg, lo, hi, k0, k1, x) == Tie(best, at[0], len(at), at[-1]), (msg[:8], lo, k0, k1, x)
+        for n in inside:
+            assert masked_min(msg, lo, hi, 32, 32, H(n)) == Tie(0, n, 1, n)
+        for n in outside:
+            assert masked_min(msg, lo, hi, 32, 32, H(n)).hash != 0
+        assert masked_min(msg, hi, hi, 32, 32, H(hi) ^ U64) == Tie(U64, hi, 1, hi)   # the all-ones hash
 
 
 def fast_kernels_of(co):
@@ -115,6 +142,8 @@ def test_variant_code_object_holds_the_kernels_and_the_marker():
     emb = codeobj.fast_code_object()
     assert fast_kernels_of(emb) == KERNELS
     assert b"mh_fast_hash_keep" not in emb
+    # the hash-XOR word (MINEHIP_DEV_HASH_XOR): the variant's kernels read it, the product's have none
+    assert b"mh_dev_hash_xor" in keep and b"mh_dev_hash_xor" not in emb
     fast = [k for k in codeobj.metadata(keep)["amdhsa.kernels"] if "fast_search" in k[".name"]]
     assert {k[".args"][0][".size"] for k in fast} == {520}      # the same FastArgs, by value
 
@@ -131,14 +160,16 @@ out = []
 for j in spec["jobs"]:
     for env in j["envs"]:
         for k0, k1 in j["keeps"]:
-            kv = dict({{k: str(v) for k, v in env.items()}}, MINEHIP_DEV_HASH_KEEP="%d,%d" % (k0, k1))
+          for x in j.get("xors", [0]):
+            kv = dict({{k: str(v) for k, v in env.items()}}, MINEHIP_DEV_HASH_KEEP="%d,%d" % (k0, k1),
+                      MINEHIP_DEV_HASH_XOR="%016x" % x)
             os.environ.update(kv)
             try:
                 if j["call"] == "batch":
-                    plan = minehip.batch_plan([(bytes.fromhex(m), lo, hi) for m, lo, hi in j["reqs"]])
-                    kinds = dict((it["req"], it["kind"]) for it in plan)
-                    assert [kinds[i] for i in range(len(j["reqs"]))] == j["kinds"], kinds
-                    r = minehip.search_batch([(bytes.fromhex(m), lo, hi) for m, lo, hi in j["reqs"]])
+                    reqs = [(bytes.fromhex(m), lo, hi) for m, lo, hi in j["reqs"]]
+                    kinds = dict((it["req"], it["kind"]) for it in minehip.batch_plan(reqs))
+                    assert [kinds[i] for i in range(len(reqs))] == j["kinds"], kinds
+                    r = minehip.search_batch(reqs)
                 elif j["call"] == "multi":
                     r = minehip.search_multi(bytes.fromhex(j["msg"]), j["lo"], j["hi"], devs=j["devs"], chunk=j["chunk"])
                 else:
@@ -152,14 +183,16 @@ print(json.dumps(dict(results=out, kernels=kernels)))
 """
 
 
-def job(msg, lo, hi, keeps, envs=({},), call="search", **kw):
-    return dict(msg=msg.hex(), lo=lo, hi=hi, keeps=[list(k) for k in keeps], envs=list(envs), call=call, **kw)
+def job(msg, lo, hi, keeps, envs=({},), call="search", xors=(0,), **kw):
+    """One search per (env, keep pair, XOR value), in that order."""
+    return dict(msg=msg.hex(), lo=lo, hi=hi, keeps=[list(k) for k in keeps], envs=list(envs), call=call,
+                xors=list(xors), **kw)
 
 
 def run_jobs(tmp_path, jobs, profile=False, timeout=120, **env):
     """Run the jobs in one child process on the dev build with the variant code object; returns
-    ([result per (job, env, keep pair), in that order], kernel set).  MINEHIP_DEV_HASH_KEEP is
-    read by every search, so one child runs every setting."""
+    ([result per (job, env, keep pair, XOR value), in that order], kernel set).  MINEHIP_DEV_HASH_KEEP
+    and MINEHIP_DEV_HASH_XOR are read by every search, so one child runs every setting."""
     assert os.path.exists(KEEP_CO), "make all builds it"
     path = str(tmp_path / "jobs.json")
     with open(path, "w") as f:
@@ -171,19 +204,22 @@ def run_jobs(tmp_path, jobs, profile=False, timeout=120, **env):
 
 
 def check_jobs(jobs, results):
-    """Every search result against masked_min.  Returns {keep pair: [Tie per job]}."""
+    """Every search result against masked_min.  Returns {keep pair: [Tie per (job, XOR value)]}."""
     ties = collections.defaultdict(list)
     it = iter(results)
     for j in jobs:
         msg = bytes.fromhex(j["msg"])
+        xors = j.get("xors", [0])
+        exps = {(k0, k1, x): masked_min(msg, j["lo"], j["hi"], k0, k1, x) for k0, k1 in j["keeps"] for x in xors}
         for env in j["envs"]:
             for k0, k1 in j["keeps"]:
-                exp = masked_min(msg, j["lo"], j["hi"], k0, k1)
-                got = tuple(next(it))
-                assert got == (exp.hash, exp.nonce), (msg[:8], len(msg), j["lo"], j["hi"], (k0, k1), env, j["call"],
-                                                     got, exp)
+                for x in xors:
+                    exp = exps[(k0, k1, x)]
+                    got = tuple(next(it))
+                    assert got == (exp.hash, exp.nonce), (msg[:8], len(msg), j["lo"], j["hi"], (k0, k1), "%016x" % x,
+                                                         env, j["call"], got, exp)
         for k0, k1 in j["keeps"]:
-            ties[(k0, k1)].append(masked_min(msg, j["lo"], j["hi"], k0, k1))
+            ties[(k0, k1)].extend(exps[(k0, k1, x)] for x in xors)
     assert next(it, None) is None
     return ties
 
