@@ -1,6 +1,6 @@
 """add3_split.py -- the add3 split of the fast_search build (Makefile, before issue_prio.py).
 
-    python3 add3_split.py K in.s out.s
+    python3 add3_split.py K in.s out.s [like_split.s]
 
 Inside every fast_search kernel of the gfx950 assembly, every K-th `v_add3_u32 d, a, b, c`
 (counted from the kernel's entry) becomes two full-rate adds, `d = x + y; d = z + d`, where z is
@@ -12,6 +12,12 @@ per-nonce loop needs at least max(H, N/2) quad-cycles (H half-rate of N instruct
 the price of one more instruction.  The chip runs this kernel at its power limit, so fewer
 quad-cycles per nonce come back partly as a lower clock; measured with the in-kernel clock probe,
 every 4th add3 split ran 5% fewer quad-cycles per nonce at a 4% lower clock.
+
+like_split.s (the first-hit build, -DMH_FIRST: the product's split assembly): the count of a kernel
+whose <J, MODE> that file also holds starts at the phase 0..K-1 at which its per-nonce loop keeps as
+many v_add3 as that kernel's loop there.  The two builds' loops hold the same instructions, but the
+code before them differs by a few add3, which would shift "every K-th" by one inside the loop: one
+add3 more or less split than in the product's loop.
 """
 import re
 import sys
@@ -42,10 +48,14 @@ def split_line(m):
     return [first, f"{ind}v_add_u32_e32 {d}, {last}, {d}"]
 
 
-def split(text, k, pattern=None):
+# entry label of a fast kernel: fast_search<J, MODE>, or first_scan<J, MODE> of the -DMH_FIRST build
+KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan)\S*:")
+
+
+def split(text, k, pattern=None, phase=None):
     """Returns (text, add3 split).  Splits every k-th v_add3 of each fast kernel (k <= 0: none),
     or, with `pattern` (a string of 0/1 repeated over each kernel's add3s, e.g. "001" = k 3),
-    those at a '1'."""
+    those at a '1'.  phase: {kernel label: add3s the count of that kernel starts at} (default 0)."""
     if pattern is None:
         if k <= 0:
             return text, 0
@@ -54,8 +64,8 @@ def split(text, k, pattern=None):
         return text, 0
     out, n, i, inside = [], 0, 0, False
     for line in text.split("\n"):
-        if re.match(r"^_ZN2mh11fast_search\S*:", line):
-            inside, i = True, 0
+        if KERNEL.match(line):
+            inside, i = True, (phase or {}).get(line.split(":")[0], 0)
         elif line.startswith(".Lfunc_end"):
             inside = False
         m = ADD3.match(line) if inside else None
@@ -88,7 +98,7 @@ def split_by_slack(text, frac, horizon=400):
     out, n = [], 0
     i = 0
     while i < len(lines):
-        if not re.match(r"^_ZN2mh11fast_search\S*:", lines[i]):
+        if not KERNEL.match(lines[i]):
             out.append(lines[i])
             i += 1
             continue
@@ -123,9 +133,38 @@ def split_by_slack(text, frac, horizon=400):
     return "\n".join(out), n
 
 
+def layout_of(label):
+    m = re.search(r"ILi(\d+)ELi(\d+)EE", label)
+    return m.groups() if m else None
+
+
+def loop_add3(text):
+    """{kernel label: v_add3 left in its per-nonce loop}."""
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import loop_mix
+    return {name: sum(o == "v_add3_u32" for o in loop_mix.per_nonce_loop(body))
+            for name, body in loop_mix.kernels(text).items() if KERNEL.match(name + ":")}
+
+
+def phases_like(text, k, like):
+    """Per kernel of `text`, the phase at which its per-nonce loop keeps as many add3 as the loop
+    of the same <J, MODE> in the split assembly `like` (no such phase, or no such kernel: 0)."""
+    want = {layout_of(name): n for name, n in loop_add3(like).items()}
+    phase = {}
+    for ph in reversed(range(max(k, 1))):   # the lowest matching phase wins
+        got = loop_add3(split(text, k, phase={name: ph for name in loop_add3(text)})[0])
+        for name, n in got.items():
+            if want.get(layout_of(name)) == n:
+                phase[name] = ph
+    return phase
+
+
 def main():
     k, src, dst = int(sys.argv[1]), sys.argv[2], sys.argv[3]
-    text, n = split(open(src).read(), k)
+    text = open(src).read()
+    phase = phases_like(text, k, open(sys.argv[4]).read()) if len(sys.argv) > 4 else None
+    text, n = split(text, k, phase=phase)
     open(dst, "w").write(text)
     print(f"add3_split: {n} v_add3_u32 of the fast kernels split (every {k}th of each) -> {dst}")
 

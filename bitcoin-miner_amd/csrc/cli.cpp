@@ -1,11 +1,14 @@
 // cli.cpp -- native command-line front ends of libminehip (C++ callers of the
 // C-ABI in include/minehip.h; no Python, no torch).
 //
-//   minehip-search <message> <maxNonce> [lower]
+//   minehip-search <message> <maxNonce> [lower [target]]
 //       scans [lower (default 0), maxNonce] on every visible GPU and prints
 //       "Result <hash> <nonce>" -- the output format of the reference client
 //       (bitcoin/client/client.go:41-43), whose argument convention
 //       (client.go:12-19: <message> <maxNonce>) it follows minus the hostport.
+//       With a target (no reference counterpart): the smallest nonce of the range
+//       whose hash is <= target, on device 0 (mh_search_first): "First <hash> <nonce>",
+//       or "None <hash> <nonce>" with the range's minimum when no nonce qualifies.
 //
 // The miner, server and client processes over LSP are apps/*_main.cpp.
 #include <errno.h>
@@ -39,23 +42,36 @@ std::vector<int> all_devices() {
 }
 
 int run_search(int argc, char** argv) {
-    if (argc != 3 && argc != 4) {
-        printf("Usage: ./%s <message> <maxNonce> [lower]", argv[0]);
+    if (argc < 3 || argc > 5) {
+        printf("Usage: ./%s <message> <maxNonce> [lower [target]]", argv[0]);
         return 2;
     }
-    uint64_t hi = 0, lo = 0;
+    uint64_t hi = 0, lo = 0, target = 0;
     if (!parse_u64(argv[2], &hi)) {
         printf("%s is not a number.\n", argv[2]);
         return 2;
     }
-    if (argc == 4 && !parse_u64(argv[3], &lo)) {
+    if (argc >= 4 && !parse_u64(argv[3], &lo)) {
         printf("%s is not a number.\n", argv[3]);
+        return 2;
+    }
+    if (argc == 5 && !parse_u64(argv[4], &target)) {
+        printf("%s is not a number.\n", argv[4]);
         return 2;
     }
     const std::vector<int> devs = all_devices();
     if (devs.empty()) {
         fprintf(stderr, "minehip: no HIP device\n");
         return 1;
+    }
+    if (argc == 5) {
+        mh_first f;
+        if (mh_search_first(0, (const uint8_t*)argv[1], strlen(argv[1]), lo, hi, target, &f) != MH_OK) {
+            fprintf(stderr, "minehip: %s\n", mh_last_error());
+            return 1;
+        }
+        printf("%s %llu %llu\n", f.found ? "First" : "None", (unsigned long long)f.hash, (unsigned long long)f.nonce);
+        return 0;
     }
     uint64_t h = 0, n = 0;
     const int rc = mh_search_multi(devs.data(), (int)devs.size(), (const uint8_t*)argv[1], strlen(argv[1]), lo,

@@ -1,6 +1,9 @@
 /* fast_co.S -- embeds the fast_search code object (fast_search.hip after the
    issue-priority pass, built by the Makefile into build/fast_search.hsaco) in
-   libminehip.so.  search_kernels.hip loads it per device (hipModuleLoadData). */
+   libminehip.so.  search_kernels.hip loads it per device (hipModuleLoadData).
+   Next to it, as a blob of its own, the first-hit kernels of mh_search_first
+   (the same source with -DMH_FIRST through the same passes,
+   build/fast_first.hsaco), loaded per device by the first mh_search_first. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -10,4 +13,12 @@ mh_fast_co_begin:
     .globl mh_fast_co_end
 mh_fast_co_end:
     .size mh_fast_co_begin, mh_fast_co_end - mh_fast_co_begin
+    .p2align 12
+    .globl mh_first_co_begin
+    .type mh_first_co_begin, @object
+mh_first_co_begin:
+    .incbin "fast_first.hsaco"
+    .globl mh_first_co_end
+mh_first_co_end:
+    .size mh_first_co_begin, mh_first_co_end - mh_first_co_begin
     .section .note.GNU-stack,"",@progbits

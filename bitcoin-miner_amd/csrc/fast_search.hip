@@ -17,7 +17,9 @@
 // which loads it per device (search_kernels.hip, fast_module).  It is never
 // part of the library's fat binary.  -DMH_HASH_KEEP builds the coarse-hash test variant
 // (build/fast_search_keep.hsaco, through the same passes), which only the dev
-// build's MINEHIP_DEV_CODE_OBJECT hook ever loads.
+// build's MINEHIP_DEV_CODE_OBJECT hook ever loads.  -DMH_FIRST builds the first-hit kernels
+// first_scan<J, MODE> (build/fast_first.hsaco, through the same passes), embedded as a
+// second code object that mh_search_first loads; without it nothing below differs from before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -165,6 +167,20 @@ __device__ __attribute__((used)) uint32_t mh_dev_hash_xor[2];
 // J and the group digits sit right before it in word J, so no word but J changes inside a run:
 // rounds 0..J-1 and every schedule word that does not depend on W[J] are run-level; otherwise
 // the per-nonce digit is the last one (word J) and the group digits lie in words J - 1 and J.
+#ifdef MH_FIRST
+// The parameters of first_scan<J, MODE> (below) as the kernarg segment holds them.
+struct FirstKernArgs {
+    FastArgs a;
+    Partial* partials;
+    FirstArgs f;
+};
+// The first-hit parameters of the kernel whose FastArgs `a` is: they follow it in the kernarg
+// segment, so the chunk body reads them through the pointer it already holds (the rare candidate
+// branch and the chunk's end only).
+__device__ __forceinline__ const FirstArgs& first_args(const FastArgs& a) {
+    return ((const FirstKernArgs*)&a)->f;
+}
+#endif
 template <int J, int MODE>
 __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restrict__ partials, const uint32_t blk) {
     using namespace dev;
@@ -264,6 +280,18 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
     const uint64_t wave_u0 = a.u_start + (uint64_t)blk * kBlockThreads + wave * 64u;
     uint32_t wbh0 = 0xFFFFFFFFu, wbh1 = 0xFFFFFFFFu;
     uint64_t wbn = ~0ull;
+#ifdef MH_FIRST
+    // First-hit variant: the wave's best is a key (k0, k1) -- (0, 0) for a nonce whose hash is <=
+    // the target (a hit), else the hash -- and a lane is a candidate when its H0 <= lim =
+    // max(k0, target >> 32): without a hit so far that admits what the product admits and every
+    // possible hit, after one (k0 = 0) only possible hits.  The loop carries lim in wbh0's place,
+    // not beside it (one more SGPR across the per-nonce loop costs the loop VALU instructions: the
+    // compiler then stops hoisting K[t] + W[t] sums out of it), and the rare branch rebuilds k0
+    // from it.  With thi = target >> 32: a key that is a hash has k0 >= thi (it is > target), so
+    // without a hit lim = k0; with one, lim = thi and k1 = 0 -- and no hash-key has k0 = thi and
+    // k1 = 0, since that is <= target.  Hence  hit <=> (lim == thi and k1 == 0),  k0 = hit ? 0 : lim.
+    // Below, wbh0 is lim outside the rare branch and k0 inside it; wbh1 is k1.
+#endif
 #ifdef MH_HASH_KEEP
     // coarse-hash variant (build/fast_search_keep.hsaco, layout.hpp keep_word): the bits of H0 and
     // H1 that enter the comparisons below; the comparisons themselves are the product's
@@ -372,7 +400,7 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
 #endif
             // New wave best (rare): a uniform branch, so H1 and the
             // lexicographic compare cost nothing on the common path.
-            uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= wbh0) & valid_mask;
+            uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= wbh0) & valid_mask;  // MH_FIRST: h0 <= lim
             if (__builtin_expect(cm != 0ull, 0)) {
 #ifdef MH_HASH_KEEP
                 const uint32_t h1 = ((st[1] + a63) ^ xor1) & keep1;
@@ -380,6 +408,34 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 const uint32_t h1 = st[1] + a63;
 #endif
                 const uint32_t q = g * 10u + i;
+#ifdef MH_FIRST
+                // The hits of this step: all take key 0, and the lowest lane holds the smallest
+                // nonce of them (at one (g, i) the nonce grows with the lane: spread is monotonic),
+                // so that lane alone is compared, on a path of its own (few scalars live beside
+                // the loop's).  Without a hit the keys are the hashes and the product's selection
+                // below applies.
+                uint64_t hm;
+                {
+                    const uint64_t target = first_args(a).target;
+                    const uint32_t thi = (uint32_t)(target >> 32), tlo = (uint32_t)target;
+                    hm = __builtin_amdgcn_ballot_w64(h0 < thi || (h0 == thi && h1 <= tlo)) & cm;
+                    if (wbh0 == thi && wbh1 == 0u) wbh0 = 0u;  // lim -> k0 (above)
+                }
+                if (hm) {
+                    const uint32_t l = (uint32_t)__builtin_ctzll(hm);
+                    uint64_t cn;
+                    if constexpr (!EARLY)
+                        cn = (wave_u0 + l) * a.pow10L + q;
+                    else
+                        cn = spread(wave_u0 + l, a.hole, a.hole_w) * a.u_mul + spread(g, a.g_hole, 1u) * a.g_mul +
+                             i * a.i_mul;
+                    if ((wbh0 | wbh1) != 0u || cn < wbn) {  // the wave's first hit, or a smaller nonce than its hit's
+                        wbh0 = 0u;
+                        wbh1 = 0u;
+                        wbn = cn;
+                    }
+                } else {
+#endif
                 // Many candidates (the first nonce of a run makes every lane one): keep only
                 // the lanes holding their smallest H0, found by a DPP wave-min, instead of a
                 // 64-step scalar scan (~1,000 serial SALU / readlane instructions per run).
@@ -406,6 +462,13 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                         wbn = cn;
                     }
                 } while (m);
+#ifdef MH_FIRST
+                }
+                {  // k0 -> lim
+                    const uint32_t thi = (uint32_t)(first_args(a).target >> 32);
+                    wbh0 = wbh0 > thi ? wbh0 : thi;
+                }
+#endif
             }
         }
     }
@@ -413,10 +476,20 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
 #undef MH_G
 #undef MH_R
 
+#ifdef MH_FIRST
+    if (wbh0 == (uint32_t)(first_args(a).target >> 32) && wbh1 == 0u) wbh0 = 0u;  // lim -> k0
+#endif
     uint64_t hash = ((uint64_t)wbh0 << 32) | wbh1;  // wave-uniform: the wave step of block_min
     uint64_t nonce = wbn;                            // is a no-op, the LDS step joins the waves
     block_min(hash, nonce);
     if (threadIdx.x == 0) partials[blk] = Partial{hash, nonce};
+#ifdef MH_FIRST
+    if (threadIdx.x == 0) {
+        const FirstArgs& f = first_args(a);
+        // key 0: the chunk's smallest qualifying nonce, for later claims to skip what lies above it
+        if (hash == 0ull) atomicMin(f.first, (unsigned long long)nonce);
+    }
+#endif
 }
 
 // The chunk the workgroup runs next: thread 0 takes it from the launch's counter (a vector
@@ -430,6 +503,7 @@ __device__ __forceinline__ uint32_t claim_chunk(uint32_t* counter) {
     return blk;
 }
 
+#ifndef MH_FIRST
 template <int J, int MODE>
 __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void fast_search(const FastArgs a,
                                                                            Partial* __restrict__ partials) {
@@ -450,6 +524,88 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void fast_search
         blk = claim_chunk(a.counter);
     }
 }
+#else
+// ---------------------------------------------------------------------------
+// first_scan<J, MODE>: the same chunks, for mh_search_first
+// ---------------------------------------------------------------------------
+// No nonce of chunk blk is smaller: lane 0's first.  Last-digit layouts: run U's nonces are
+// U * 10^L + q.  Early layouts: nonce(U, g, i) = spread(U) * u_mul + (terms >= 0 of g and i), and
+// spread is strictly increasing in U, so the chunk's smallest U at g = i = 0 bounds every lane's
+// interleaved nonces from below (it is attained, so the bound is exact).
+template <int MODE>
+__device__ __forceinline__ uint64_t chunk_floor(const FastArgs& a, uint32_t blk) {
+    const uint64_t u0 = a.u_start + (uint64_t)blk * kBlockThreads;
+    if constexpr (MODE < (int)kModeOneEarly)
+        return u0 * a.pow10L;
+    else
+        return spread(u0, a.hole, a.hole_w) * a.u_mul;
+}
+
+// claim_chunk with one more word per claim: thread 0 reads *f.first, the smallest qualifying
+// nonce any finished chunk of this search has reported (all ones: none), beside the claim; a chunk
+// all of whose nonces are larger is skipped -- thread 0 writes the sentinel its slot's merge
+// expects and claims again -- so the workgroup only ever sees a chunk to run, or the end.  The word
+// only ever decreases and always holds a qualifying nonce of the range, so the chunk of the
+// smallest qualifying nonce and every chunk holding a smaller nonce are never skipped, whatever
+// value a claim happens to see: a stale read only skips less.  Static launches (no counter): the
+// workgroup's one chunk is blockIdx.x, and skipping it ends the workgroup.
+template <int MODE>
+__device__ __forceinline__ uint32_t claim_first(Partial* __restrict__ partials) {
+    __shared__ uint32_t s_next;
+    if (threadIdx.x == 0) {
+        uint32_t b;
+        for (;;) {
+            // the arguments through a pointer laundered per claim, as the chunk body's: vector
+            // copies of values derived from them, hoisted out of the kernel's loop, cost every
+            // layout 4 VGPRs across the chunk
+            using KArgs = __attribute__((address_space(4))) const FirstKernArgs;
+            KArgs* k = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(k));
+            const FastArgs& a = ((const FirstKernArgs*)k)->a;
+            const FirstArgs& f = ((const FirstKernArgs*)k)->f;
+            b = a.counter ? atomicAdd(a.counter, 1u) : blockIdx.x;
+            if (b >= a.n_chunks) break;
+            const uint64_t seen = __hip_atomic_load(f.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (chunk_floor<MODE>(a, b) <= seen) {
+                // this chunk will be run: its valid nonces count as scanned
+                const uint32_t left = a.n_runs - b * (uint32_t)kBlockThreads;  // b < n_chunks: >= 1
+                const uint32_t lanes = left < (uint32_t)kBlockThreads ? left : (uint32_t)kBlockThreads;
+                atomicAdd(f.scanned, (unsigned long long)lanes * a.n_groups * 10ull);
+                break;
+            }
+            uint64_t ones = ~0ull;
+            asm volatile("" : "+v"(ones));  // made here: hoisted, the sentinel held 4 VGPRs across the chunk
+            partials[b] = Partial{ones, ones};
+            if (!a.counter) {
+                b = ~0u;  // past every n_chunks
+                break;
+            }
+        }
+        s_next = b;
+    }
+    __syncthreads();
+    const uint32_t blk = __builtin_amdgcn_readfirstlane(s_next);  // one value per workgroup: scalar
+    __syncthreads();  // every wave has read it before thread 0 may overwrite it
+    return blk;
+}
+
+// fast_search's loop over claim_first: every chunk the loop sees is run.
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void first_scan(const FastArgs a,
+                                                                          Partial* __restrict__ partials,
+                                                                          const FirstArgs) {
+    using KArgs = __attribute__((address_space(4))) const FirstKernArgs;
+    KArgs* const kp = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t blk = claim_first<MODE>(partials);
+    while (blk < a.n_chunks) {
+        KArgs* k = kp;
+        asm volatile("" : "+s"(k));
+        fast_chunk<J, MODE>(((const FirstKernArgs*)k)->a, partials, blk);
+        if (!a.counter) break;
+        blk = claim_first<MODE>(partials);
+    }
+}
+#endif
 
 // Marker of a code object whose fast_search kernels run the work-queue loop above over this
 // FastArgs layout: its size is sizeof(FastArgs).  The library uses the work queue with a code
@@ -472,7 +628,12 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 // 64..82), kModeTwo for J = 13..15 of block 0; the Early modes where a nonce
 // costs less with the digit ending word J innermost than with the last digit
 // in word J + 1 (plan.cpp: nonce_cost(J) < nonce_cost(J + 1)).
+#ifndef MH_FIRST
 #define MH_INST(j, m) template __global__ void fast_search<j, m>(const FastArgs, Partial* __restrict__);
+#else
+#define MH_INST(j, m) \
+    template __global__ void first_scan<j, m>(const FastArgs, Partial* __restrict__, const FirstArgs);
+#endif
 MH_FAST_KERNELS(MH_INST)  // layout.hpp: the one list of instantiated layouts
 #undef MH_INST
 

@@ -137,6 +137,18 @@ struct GenArgs {
     uint32_t pad;         // 0; dev build: the coarse-hash word (keep_word above)
 };
 
+// ---- first-hit search (mh_search_first) ----
+// Extra kernel parameters of the first-hit scan kernels (first_scan<J, MODE> of the
+// build/fast_first.hsaco code object, generic_scan_first), after the product kernels' own two;
+// FastArgs and GenArgs stay as they are.  A nonce's key is 0 if Hash <= target, else Hash: the
+// lexicographic minimum of (key, nonce) is the smallest qualifying nonce, or without one the
+// product's (Hash, nonce) minimum, so Partial, block_min and merge_partials serve unchanged.
+struct FirstArgs {
+    uint64_t target;
+    unsigned long long* first;    // smallest qualifying nonce found so far; all ones: none yet
+    unsigned long long* scanned;  // valid nonces of the chunks / workgroups that were not skipped
+};
+
 // ---- batched search (batch_scan / merge_segments) ----
 // Many small Requests in one launch.  A lane's unit of work is an aligned decade, the ten nonces
 // 10u .. 10u+9: they share their digit count, so u is formatted once for the ten.  A tile is one

@@ -57,13 +57,15 @@ def inner_loop(body):
 
 
 FAST = re.compile(r"^_ZN2mh11fast_searchILi(\d+)ELi(\d+)EE")
+FIRST = re.compile(r"^_ZN2mh10first_scanILi(\d+)ELi(\d+)EE")  # the -DMH_FIRST build's kernels (build/fast_first_prio.s)
 
 
-def loop_mix(text):
-    """{"J,MODE": {"valu": N, "half": H}} of every fast_search kernel's per-nonce loop."""
+def loop_mix(text, pattern=FAST):
+    """{"J,MODE": {"valu": N, "half": H}} of every fast_search kernel's per-nonce loop (pattern:
+    the kernels' mangled names, J and MODE as its groups)."""
     out = {}
     for name, body in kernels(text).items():
-        m = FAST.match(name)
+        m = pattern.match(name)
         if not m:
             continue
         ins = [x for x in inner_loop(body) if x != "s_setprio"]

@@ -42,6 +42,12 @@ hipError_t launch_generic_scan(const GenArgs& a, Partial* partials, uint32_t blo
 hipError_t launch_hash_batch(const GenArgs& a, const uint64_t* d_nonces, uint64_t* d_out, uint64_t n,
                              hipStream_t s);
 hipError_t launch_merge(const Partial* partials, uint32_t n, Partial* best, hipStream_t s);
+hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partial* partials, const FirstArgs& f,
+                             hipStream_t s);
+hipError_t launch_generic_scan_first(const GenArgs& a, Partial* partials, uint32_t blocks, const FirstArgs& f,
+                                     hipStream_t s);
+hipError_t launch_finish_first(const GenArgs& a, const Partial* best, const unsigned long long* scanned, uint64_t* out,
+                               hipStream_t s);
 hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials, uint32_t tiles,
                              hipStream_t s);
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
@@ -114,6 +120,10 @@ struct DevCtx {
     uint8_t* h_btab = nullptr;  // pinned staging of the same bytes
     Partial* d_bres = nullptr;  // one result per request of the passes in flight
     Partial* h_bres = nullptr;  // pinned
+    // first-hit search (mh_search_first), allocated by the first such call
+    uint64_t* d_first = nullptr;  // [0] smallest qualifying nonce so far, [1] nonces scanned, [2..4] the result
+    uint64_t* h_first = nullptr;  // pinned: hash, nonce, scanned
+    const mh::FirstArgs* first = nullptr;  // set while an mh_search_first enqueues its pieces
 #ifdef MH_DEV_HOOKS
     uint32_t keep = 0;        // this call's coarse-hash word (MINEHIP_DEV_HASH_KEEP; 0: unset)
     bool keep_fast = false;   // ... and the fast code object in use is the variant that reads it
@@ -355,7 +365,12 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
         tm->var = p.kind == 0 ? var_index(p.J, p.mode, p.L) : 0;
         MH_HIP(hipEventRecord(tm->start, s));
     }
-    if (p.kind == 0)
+    if (c->first) {  // mh_search_first: the first-hit kernels over the same pieces
+        if (p.kind == 0)
+            MH_HIP(mh::launch_fast_first(c->dev, p.J, p.mode, fa, out, *c->first, s));
+        else
+            MH_HIP(mh::launch_generic_scan_first(ga, out, blocks, *c->first, s));
+    } else if (p.kind == 0)
         MH_HIP(mh::launch_fast(c->dev, p.J, p.mode, fa, out, s));
     else
         MH_HIP(mh::launch_generic_scan(ga, out, blocks, s));
@@ -492,6 +507,74 @@ int search_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, 
     *oh = c->h_best->hash;
     *on = c->h_best->nonce;
     if (busy_ns) *busy_ns = now_ns() - t0;
+    return MH_OK;
+}
+
+// mh_search_first: search_impl's plan, streams, partial flushes and work-queue counters over the
+// first-hit kernels (first_scan<J, MODE>, generic_scan_first; layout.hpp FirstArgs), then
+// finish_first on the main stream and one 24-byte copy-back with the one synchronise.  The word
+// the kernels skip later chunks by and the scanned count are reset beside the running minimum.
+int search_first_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, mh_first* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    if (!c->d_first) MH_HIP(hipMalloc(&c->d_first, 5 * sizeof(uint64_t)));
+    if (!c->h_first) MH_HIP(hipHostMalloc(&c->h_first, 3 * sizeof(uint64_t), hipHostMallocDefault));
+#ifdef MH_DEV_HOOKS
+    c->keep = 0;  // mh_search_first refused the hash hooks; nothing of an earlier search's stays
+    c->keep_fast = c->xor_on = c->xor_fast = false;
+#endif
+    MH_HIP(hipMemsetAsync(c->d_best, 0xFF, sizeof(Partial), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_first, 0xFF, sizeof(uint64_t), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_first + 1, 0, sizeof(uint64_t), c->stream));
+    const mh::PlanOpts opt = plan_opts();
+    if (opt.queue) MH_HIP(hipMemsetAsync(c->d_counters, 0, sizeof(uint32_t) * kQueueSlots, c->stream));
+    c->qoff = 0;
+    bool any_coarse = false, any_fine = false;
+    if (opt.streams == 2)
+        mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
+            (coarse_piece(p, opt) ? any_coarse : any_fine) = true;
+            return !(any_coarse && any_fine);
+        });
+    const bool split = opt.streams == 2 && any_coarse && any_fine;
+    if (split) {
+        rc = piece_streams_wait_main(c);
+        if (rc) return rc;
+    }
+    const mh::FirstArgs fargs{target, (unsigned long long*)c->d_first, (unsigned long long*)(c->d_first + 1)};
+    int err = MH_OK;
+    c->poff = 0;
+    c->first = &fargs;
+    mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
+        err = enqueue_piece(c, p, opt, split);
+        return err == MH_OK;
+    });
+    c->first = nullptr;
+    if (!err) err = flush_partials(c, split);
+    if (err) {
+        for (auto ps : c->ps)
+            if (ps) (void)hipStreamSynchronize(ps);
+        (void)hipStreamSynchronize(c->stream);
+        return err;
+    }
+    mh::GenArgs ga;
+    mh::make_gen_args(pre, &ga);
+    MH_HIP(mh::launch_finish_first(ga, c->d_best, (const unsigned long long*)(c->d_first + 1), c->d_first + 2, c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_first, c->d_first + 2, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    out->hash = c->h_first[0];
+    out->nonce = c->h_first[1];
+    out->scanned = c->h_first[2];
+    out->found = out->hash <= target ? 1 : 0;  // without a qualifying nonce the minimum itself is > target
+    out->reserved = 0;
     return MH_OK;
 }
 
@@ -681,6 +764,24 @@ int mh_search(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t 
     mh::Prefix pre;
     mh::absorb_prefix(msg, len, &pre);
     return search_impl(dev, pre, lower, upper, out_hash, out_nonce);
+}
+
+int mh_search_first(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                    mh_first* out) {
+    g_err.clear();
+    if (!out) return fail(MH_EINVAL, "NULL output pointer");
+    int rc = check_common(msg, len);
+    if (rc) return rc;
+    if (lower > upper) return fail(MH_ERANGE, "lower > upper");
+#ifdef MH_DEV_HOOKS
+    // the first-hit kernels have no variants of these hooks: refuse, never ignore them
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_first does not support ") + hook);
+#endif
+    mh::Prefix pre;
+    mh::absorb_prefix(msg, len, &pre);
+    return search_first_impl(dev, pre, lower, upper, target, out);
 }
 
 int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,

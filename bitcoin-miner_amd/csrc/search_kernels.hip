@@ -20,6 +20,11 @@
 //                         decades of ten nonces formatted once (mh_search_batch).
 //   merge_segments        one workgroup per request of a batch pass folds that
 //                         request's slot segment into its result.
+//   first_scan<J, MODE>   (fast_search.hip, -DMH_FIRST) fast_search for mh_search_first: the
+//                         smallest nonce whose hash is <= a target, later chunks skipped; a
+//                         second embedded code object, loaded by the first such search.
+//   generic_scan_first    generic_scan for mh_search_first.
+//   finish_first          one thread: the winning key back into its hash, the result out.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -40,6 +45,8 @@
 
 // fast_search.hip's code object after the issue-priority pass (fast_co.S)
 extern "C" const unsigned char mh_fast_co_begin[];
+// the same source built with -DMH_FIRST: first_scan<J, MODE>, the fast kernels of mh_search_first
+extern "C" const unsigned char mh_first_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -116,6 +123,57 @@ __global__ __launch_bounds__(kBlockThreads) void generic_scan(const GenArgs a, P
     }
     block_min(hash, nonce);
     if (threadIdx.x == 0) partials[blockIdx.x] = Partial{hash, nonce};
+}
+
+// generic_scan for mh_search_first: a nonce's key is 0 if its hash is <= f.target,
+// else the hash.  The workgroup is skipped when its first nonce -- its smallest -- is larger than
+// *f.first, the smallest qualifying nonce reported so far (the skip rule of first_scan,
+// fast_search.hip); it then writes the sentinel the merge reads.  No test hooks: mh_search_first
+// refuses them.
+__global__ __launch_bounds__(kBlockThreads) void generic_scan_first(const GenArgs a, Partial* __restrict__ partials,
+                                                                    const FirstArgs f) {
+    using namespace dev;
+    __shared__ uint32_t s_skip;
+    const uint64_t base = a.first + (uint64_t)blockIdx.x * kBlockThreads;  // a valid nonce: blocks = ceil(count / 256)
+    if (threadIdx.x == 0)
+        s_skip = base > __hip_atomic_load(f.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
+    __syncthreads();
+    if (s_skip) {  // one value per workgroup
+        if (threadIdx.x == 0) partials[blockIdx.x] = Partial{~0ull, ~0ull};
+        return;
+    }
+    const uint64_t n = base + threadIdx.x;
+    uint32_t h0, h1;
+    hash_generic(a, n, h0, h1);
+    uint64_t hash = ((uint64_t)h0 << 32) | h1, nonce = n;
+    if (hash <= f.target) hash = 0ull;
+    const uint64_t left = a.count - (uint64_t)blockIdx.x * kBlockThreads;  // >= 1
+    if (threadIdx.x >= left) {
+        hash = ~0ull;
+        nonce = ~0ull;
+    }
+    block_min(hash, nonce);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = Partial{hash, nonce};
+        if (hash == 0ull) atomicMin(f.first, (unsigned long long)nonce);
+        atomicAdd(f.scanned, (unsigned long long)(left < (uint64_t)kBlockThreads ? left : (uint64_t)kBlockThreads));
+    }
+}
+
+// The end of an mh_search_first, one thread on the main stream after the last merge: a winning
+// key 0 (some nonce qualified; best->nonce is the smallest) becomes that nonce's real hash again,
+// and the result leaves in one piece: out = {hash, nonce, nonces scanned}.
+__global__ void finish_first(const GenArgs a, const Partial* __restrict__ best,
+                             const unsigned long long* __restrict__ scanned, uint64_t* __restrict__ out) {
+    Partial b = *best;
+    if (b.hash == 0ull) {  // only a qualifying nonce has key 0 (the sentinel's is all ones)
+        uint32_t h0, h1;
+        dev::hash_generic(a, b.nonce, h0, h1);
+        b.hash = ((uint64_t)h0 << 32) | h1;
+    }
+    out[0] = b.hash;
+    out[1] = b.nonce;
+    out[2] = *scanned;
 }
 
 __global__ __launch_bounds__(kBlockThreads) void hash_batch(const GenArgs a, const uint64_t* __restrict__ nonces,
@@ -337,18 +395,22 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 
 // queue_ok: the code object carries fast_search.hip's mh_fast_queue_args marker at this
 // library's sizeof(FastArgs), i.e. its kernels claim chunks from a.counter
-hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr) {
+// first: the first-hit kernels first_scan<J, MODE> of the second embedded code object (module key
+// ":first", no file of that name is ever loaded), which no hook replaces
+hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr, bool first = false) {
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
-    const std::string path = (co && *co) ? co : "";
+    const std::string path = first ? ":first" : (co && *co) ? co : "";
 #else
-    const std::string path;
+    const std::string path = first ? ":first" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
     if (it == g_mods.end()) {
         hipModule_t m;
-        const hipError_t e = path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin) : hipModuleLoad(&m, path.c_str());
+        const hipError_t e = first          ? hipModuleLoadData(&m, mh_first_co_begin)
+                             : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
+                                            : hipModuleLoad(&m, path.c_str());
         if (e != hipSuccess) {
             (void)hipGetLastError();  // the failure is returned here; do not leave it for the next launch check
             return e;
@@ -376,7 +438,10 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
     auto fit = g_funcs.find({it->second, J + 16 * mode});
     if (fit == g_funcs.end()) {
         char name[96];
-        snprintf(name, sizeof name, "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE", J, mode);
+        snprintf(name, sizeof name,
+                 first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
+                       : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
+                 J, mode);
         hipFunction_t fn;
         const hipError_t e = hipModuleGetFunction(&fn, it->second, name);
         if (e != hipSuccess) {
@@ -502,6 +567,42 @@ hipError_t launch_fast(int dev, int J, int mode, const FastArgs& a, Partial* par
     Partial* out = partials;
     void* params[] = {&args, &out};
     return hipModuleLaunchKernel(f, grid, 1, 1, kBlockThreads, 1, 1, lds, s, params, nullptr);
+}
+
+// launch_fast for mh_search_first: first_scan<J, mode> of the first-hit code object (loaded on dev,
+// the current device, by the first call), the same grid rule, f as the third kernel parameter.
+hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partial* partials, const FirstArgs& f,
+                             hipStream_t s) {
+    if (!fast_variant_exists(J, mode)) return hipErrorInvalidValue;
+    hipFunction_t fn;
+    bool queue_ok = false;
+    hipError_t e = fast_function(dev, J, mode, &fn, &queue_ok, true);
+    if (e != hipSuccess) return e;
+    FastArgs args = a;
+    if (!queue_ok) args.counter = nullptr;
+    uint32_t grid = args.n_chunks;
+    if (args.counter) {
+        uint32_t resident = 0;
+        e = resident_groups(dev, fn, 0, &resident);
+        if (e != hipSuccess) return e;
+        grid = std::min(grid, resident);
+    }
+    Partial* out = partials;
+    FirstArgs fa = f;
+    void* params[] = {&args, &out, &fa};
+    return hipModuleLaunchKernel(fn, grid, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+
+hipError_t launch_generic_scan_first(const GenArgs& a, Partial* partials, uint32_t blocks, const FirstArgs& f,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(generic_scan_first, dim3(blocks), dim3(kBlockThreads), 0, s, a, partials, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_finish_first(const GenArgs& a, const Partial* best, const unsigned long long* scanned, uint64_t* out,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(finish_first, dim3(1), dim3(1), 0, s, a, best, scanned, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_generic_scan(const GenArgs& a, Partial* partials, uint32_t blocks, hipStream_t s) {

@@ -8,6 +8,8 @@ tests read like the reference (line numbers into the reference repo):
   search(msg, lower, upper)  the miner scan (stub miner.go:33)
   search_multi(...)          the scan sharded over several devices
   search_batch(requests)     many small scans fused into one GPU pass
+  search_first(msg, lower, upper, target)
+                             the smallest nonce whose hash is <= target
   miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
@@ -22,7 +24,7 @@ import numpy as np
 from ._lib import lib, mh_piece, mh_message, mh_kernel_stat, mh_span, OPS_PER_BLOCK, EXPORTS, LIB_PATH  # noqa: F401
 from ._lib import MH_OK, MH_EINVAL, MH_ERANGE, MH_ETOOLONG, MH_ENODEV, MH_EHIP  # noqa: F401
 from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
-from ._lib import mh_request, mh_result, mh_batch_item  # noqa: F401
+from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -53,6 +55,16 @@ def search(msg, lower, upper, dev=0):
     n = ctypes.c_uint64()
     _check(lib.mh_search(dev, m, len(m), lower, upper, ctypes.byref(h), ctypes.byref(n)))
     return h.value, n.value
+
+
+def search_first(msg, lower, upper, target, dev=0):
+    """(found, hash, nonce, scanned): the smallest nonce n of [lower, upper] with Hash(msg, n) <=
+    target and its hash (found True), or search()'s (hash, nonce) when none qualifies (found
+    False); scanned is how many nonces of the range were hashed (mh_search_first)."""
+    m = _b(msg)
+    out = mh_first()
+    _check(lib.mh_search_first(dev, m, len(m), lower, upper, target, ctypes.byref(out)))
+    return bool(out.found), out.hash, out.nonce, out.scanned
 
 
 def search_multi(msg, lower, upper, devs=None, chunk=0):

@@ -34,6 +34,7 @@ EXPORTS = (
     "mh_last_error", "mh_msg_encode", "mh_msg_decode", "mh_miner_handle",
     "mh_profile_enable", "mh_profile_read", "mh_profile_kernels", "mh_plan", "mh_multi_plan",
     "mh_multi_rates", "mh_search_batch", "mh_batch_plan", "mh_miner_handle_batch",
+    "mh_search_first",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -69,6 +70,11 @@ class mh_request(ctypes.Structure):
 class mh_result(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("hash", ctypes.c_uint64),
                 ("nonce", ctypes.c_uint64)]
+
+
+class mh_first(ctypes.Structure):
+    _fields_ = [("found", ctypes.c_int32), ("reserved", ctypes.c_int32), ("hash", ctypes.c_uint64),
+                ("nonce", ctypes.c_uint64), ("scanned", ctypes.c_uint64)]
 
 
 class mh_batch_item(ctypes.Structure):
@@ -139,6 +145,7 @@ def _load():
                                 ctypes.POINTER(mh_span), ctypes.c_int64]
     L.mh_multi_rates.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
     L.mh_search_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_result)]
+    L.mh_search_first.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.POINTER(mh_first)]
     L.mh_batch_plan.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_batch_item), ctypes.c_int64]
     L.mh_miner_handle_batch.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz,
                                         ctypes.c_char_p, sz, ctypes.POINTER(sz), intp]

@@ -26,6 +26,14 @@ def fast_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def first_code_object():
+    """The embedded code object of the first-hit kernels (mh_search_first): first_scan<J, MODE>,
+    fast_search.hip built with -DMH_FIRST (mh_first_co_begin .. mh_first_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_first_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_first_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def unpack_msgpack(b):
     """Decode one MessagePack object (the subset AMDGPU metadata uses: maps, arrays, strings,
     binary, integers, floats, booleans, nil).  No dependency on the msgpack package."""
@@ -109,12 +117,14 @@ def max_waves_per_simd(vgpr, agpr=0):
     return min(MAX_WAVES_PER_SIMD, VGPRS_PER_SIMD_LANE // max(alloc, VGPR_GRANULE))
 
 
-def fast_kernel_resources():
-    """{(J, MODE): {vgpr, sgpr, agpr, scratch_bytes, lds_bytes, spills, max_waves_per_simd}}."""
+def fast_kernel_resources(co=None, name=r"_ZN2mh11fast_searchILi(\d+)ELi(\d+)E"):
+    """{(J, MODE): {vgpr, sgpr, agpr, scratch_bytes, lds_bytes, spills, max_waves_per_simd}} of
+    the embedded fast_search kernels, or of the kernels of code object `co` whose names match
+    `name`."""
     import re
     out = {}
-    for k in metadata(fast_code_object())["amdhsa.kernels"]:
-        m = re.match(r"_ZN2mh11fast_searchILi(\d+)ELi(\d+)E", k[".name"])
+    for k in metadata(fast_code_object() if co is None else co)["amdhsa.kernels"]:
+        m = re.match(name, k[".name"])
         if not m:
             continue
         out[(int(m.group(1)), int(m.group(2)))] = {
@@ -124,3 +134,8 @@ def fast_kernel_resources():
             "max_waves_per_simd": max_waves_per_simd(k[".vgpr_count"], k.get(".agpr_count", 0)),
         }
     return out
+
+
+def first_kernel_resources():
+    """The same of the embedded first_scan<J, MODE> kernels."""
+    return fast_kernel_resources(first_code_object(), r"_ZN2mh10first_scanILi(\d+)ELi(\d+)E")

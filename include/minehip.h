@@ -130,6 +130,30 @@ typedef struct mh_result {
  * code and leaves out undefined.  One device only. */
 int mh_search_batch(int dev, const mh_request *reqs, size_t n, mh_result *out);
 
+/* ---- first-hit search: the smallest nonce whose hash meets a target ------ */
+
+typedef struct mh_first {
+    int32_t found, reserved;  /* 1: some nonce of the range has Hash <= target */
+    uint64_t hash, nonce;     /* found: the SMALLEST such nonce and its hash;
+                                 not found: exactly what mh_search returns   */
+    uint64_t scanned;         /* nonces of [lower, upper] actually hashed    */
+} mh_first;
+
+/* The proof-of-work question over [lower, upper] on device `dev`: the smallest nonce n with
+ * Hash(msg, n) <= target -- usually not the nonce of the range's minimum -- found without hashing
+ * the whole range: once some part of the search has found a qualifying nonce, the work that lies
+ * wholly above it is skipped.  The result is deterministic and bit-exact, whatever the launch
+ * plan, the streams, the queue mode or the timing; only `scanned` depends on them.  It is counted
+ * on the device: upper - lower + 1 when nothing qualifies (the result is then mh_search's), and
+ * always >= nonce - lower + 1 otherwise, since nothing below the answer is ever skipped.
+ * target == 2^64-1 makes every nonce qualify (the answer is lower); target == 0 only a zero hash.
+ * Errors and calling conventions as mh_search: MH_ERANGE, MH_ETOOLONG, MH_EINVAL (out == NULL
+ * too), MH_ENODEV.  Additive in ABI 5 (no existing struct changes).
+ * Out of scope: a multi-device form, a batched form, and the LSP protocol, which stays as it is
+ * (the reference's Message has no target field). */
+int mh_search_first(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
+                    uint64_t target, mh_first *out);
+
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
 
