@@ -169,4 +169,20 @@ struct BatchEntry {
     uint32_t slot0;       // first partial slot of the entry in its pass
 };
 
+// ---- batched first-hit search (batch_scan_first / merge_segments_first) ----
+// The device words of one request of a pass, in a table parallel to the segments; BatchEntry stays
+// as it is, and entry_req[entry] (a table parallel to the entries) names the request.  The key is
+// the request: two requests of one message and range with different targets have words of their
+// own.  The initial values travel in the pass's table copy.
+struct BatchFirstWords {
+    uint64_t target;
+    unsigned long long first;    // smallest qualifying nonce reported so far; all ones: none yet
+    unsigned long long scanned;  // valid nonces of the tiles that were not skipped
+};
+
+// One request's result of a pass, as merge_segments_first writes it and the host copies it back.
+struct BatchFirstResult {
+    uint64_t hash, nonce, scanned;
+};
+
 }  // namespace mh

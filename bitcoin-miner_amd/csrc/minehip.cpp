@@ -52,6 +52,12 @@ hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_ent
                              hipStream_t s);
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
                                  hipStream_t s);
+hipError_t launch_batch_scan_first(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
+                                   const uint32_t* order, BatchFirstWords* words, Partial* partials, uint32_t tiles,
+                                   hipStream_t s);
+hipError_t launch_merge_segments_first(const Partial* partials, const uint32_t* seg, const BatchEntry* entries,
+                                       const uint32_t* tile_entry, const BatchFirstWords* words,
+                                       BatchFirstResult* results, uint32_t requests, hipStream_t s);
 }  // namespace mh
 
 namespace {
@@ -120,6 +126,9 @@ struct DevCtx {
     uint8_t* h_btab = nullptr;  // pinned staging of the same bytes
     Partial* d_bres = nullptr;  // one result per request of the passes in flight
     Partial* h_bres = nullptr;  // pinned
+    // batched first-hit search (mh_search_first_batch), allocated by the first such call
+    mh::BatchFirstResult* d_fres = nullptr;  // one result per request of the passes in flight
+    mh::BatchFirstResult* h_fres = nullptr;  // pinned
     // first-hit search (mh_search_first), allocated by the first such call
     uint64_t* d_first = nullptr;  // [0] smallest qualifying nonce so far, [1] nonces scanned, [2..4] the result
     uint64_t* h_first = nullptr;  // pinned: hash, nonce, scanned
@@ -744,6 +753,148 @@ int search_batch_impl(int dev, const mh_request* reqs, size_t n, mh_result* out,
     return MH_OK;
 }
 
+// ---- batched first-hit search ----
+
+//   MINEHIP_FIRST_BATCH_ORDER  "request": workgroup b of batch_scan_first runs tile b (the identity,
+//                              request-major order) instead of the rank-major order; read per
+//                              call (measurement and tests; found, hash and nonce never depend on it)
+bool first_batch_rank_major() {
+    const char* e = getenv("MINEHIP_FIRST_BATCH_ORDER");
+    return !(e && strcmp(e, "request") == 0);
+}
+
+// The per-request checks of a batch (mh_request or mh_first_request): a status for every request,
+// and the valid ones as BatchRequests.
+template <class Req>
+void batch_requests(const Req* reqs, size_t n, std::vector<int>* status, std::vector<mh::BatchRequest>* valid) {
+    status->assign(n, MH_OK);
+    valid->clear();
+    valid->reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        int st = check_common(reqs[i].msg, reqs[i].len);
+        if (!st && reqs[i].lower > reqs[i].upper) st = fail(MH_ERANGE, "lower > upper");
+        (*status)[i] = st;
+        if (st) continue;
+        valid->emplace_back();
+        mh::BatchRequest& r = valid->back();
+        mh::absorb_prefix(reqs[i].msg, reqs[i].len, &r.pre);
+        r.lower = reqs[i].lower;
+        r.upper = reqs[i].upper;
+        r.id = i;
+    }
+}
+
+int first_batch_init_locked(DevCtx* c) {
+    if (!c->d_fres) MH_HIP(hipMalloc(&c->d_fres, sizeof(mh::BatchFirstResult) * kBatchResults));
+    if (!c->h_fres)
+        MH_HIP(hipHostMalloc(&c->h_fres, sizeof(mh::BatchFirstResult) * kBatchResults, hipHostMallocDefault));
+    return MH_OK;
+}
+
+void put_first_result(mh_first_result* r, uint64_t hash, uint64_t nonce, uint64_t scanned, uint64_t target) {
+    r->hash = hash;
+    r->nonce = nonce;
+    r->scanned = scanned;
+    r->found = hash <= target ? 1 : 0;  // without a qualifying nonce the minimum itself is > target
+}
+
+int first_batch_drain(DevCtx* c, const mh::BatchRequest* reqs, const mh_first_request* src, BatchPending* pend,
+                      mh_first_result* out) {
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        const int rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    for (size_t k = 0; k < pend->req_idx.size(); ++k) {
+        const size_t id = reqs[pend->req_idx[k]].id;
+        put_first_result(&out[id], c->h_fres[k].hash, c->h_fres[k].nonce, c->h_fres[k].scanned, src[id].target);
+    }
+    pend->req_idx.clear();
+    pend->toff = 0;
+    return MH_OK;
+}
+
+// batch_run_pass over the first-hit kernels: the pass's one H2D copy also carries the per-entry
+// request index, the dispatch order and the requests' device words with their initial values
+// (target; first = all ones; scanned = 0), so there is no memset and no fill kernel; then
+// batch_scan_first, merge_segments_first and one D2H copy of {hash, nonce, scanned} per request.
+int first_batch_run_pass(DevCtx* c, const mh::BatchRequest* reqs, const mh_first_request* src, const mh::BatchTables& t,
+                         uint32_t slot_cap, bool rank_major, BatchPending* pend, mh_first_result* out) {
+    if (!mh::batch_tables_ok(t, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+    mh::FirstBatchTables ft;
+    mh::build_first_batch_tables(t, rank_major, &ft);
+    if (!mh::first_batch_tables_ok(t, ft)) return fail(MH_EINTERNAL, "internal: bad first-hit batch tables");
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t o_seg = align16(ne * sizeof(mh::BatchEntry)), o_tile = o_seg + align16((nreq + 1u) * sizeof(uint32_t));
+    const size_t o_ereq = o_tile + align16(tiles * sizeof(uint32_t)), o_order = o_ereq + align16(ne * sizeof(uint32_t));
+    const size_t o_words = o_order + align16(tiles * sizeof(uint32_t));
+    const size_t bytes = o_words + align16(nreq * sizeof(mh::BatchFirstWords));
+    if (bytes > kBatchTableBytes || nreq > kBatchResults) return fail(MH_EINTERNAL, "internal: batch pass too large");
+    if (pend->toff + bytes > kBatchTableBytes || pend->req_idx.size() + nreq > kBatchResults ||
+        (c->prof && c->used == kEventPairs)) {
+        const int rc = first_batch_drain(c, reqs, src, pend, out);
+        if (rc) return rc;
+    }
+    uint8_t* h = c->h_btab + pend->toff;
+    uint8_t* d = c->d_btab + pend->toff;
+    memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+    memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    memcpy(h + o_ereq, ft.entry_req.data(), ne * sizeof(uint32_t));
+    memcpy(h + o_order, ft.order.data(), tiles * sizeof(uint32_t));
+    mh::BatchFirstWords* hw = (mh::BatchFirstWords*)(h + o_words);
+    for (size_t r = 0; r < nreq; ++r) hw[r] = mh::BatchFirstWords{src[reqs[t.req_idx[r]].id].target, ~0ull, 0ull};
+    MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    Timed* tm = nullptr;
+    if (c->prof) {  // generic class, with the planned nonces, as the batch launches
+        tm = &c->pool[(size_t)c->used++];
+        tm->kind = 1;
+        tm->var = 0;
+        MH_HIP(hipEventRecord(tm->start, c->stream));
+    }
+    MH_HIP(mh::launch_batch_scan_first((const mh::BatchEntry*)d, (const uint32_t*)(d + o_tile),
+                                       (const uint32_t*)(d + o_ereq), (const uint32_t*)(d + o_order),
+                                       (mh::BatchFirstWords*)(d + o_words), c->d_partials, (uint32_t)tiles, c->stream));
+    if (tm) {
+        MH_HIP(hipEventRecord(tm->stop, c->stream));
+        c->cnt[4] += t.nonces;
+    }
+    const size_t roff = pend->req_idx.size();
+    MH_HIP(mh::launch_merge_segments_first(c->d_partials, (const uint32_t*)(d + o_seg), (const mh::BatchEntry*)d,
+                                           (const uint32_t*)(d + o_tile), (const mh::BatchFirstWords*)(d + o_words),
+                                           c->d_fres + roff, (uint32_t)nreq, c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_fres + roff, c->d_fres + roff, nreq * sizeof(mh::BatchFirstResult), hipMemcpyDeviceToHost,
+                          c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    pend->toff += bytes;
+    return MH_OK;
+}
+
+// The fused passes of a first-hit batch, under the device's lock.
+int first_batch_run_fused(int dev, const mh::BatchRequest* reqs, const mh_first_request* src,
+                          const std::vector<mh::BatchItem>& items, int passes, uint32_t slot_cap, mh_first_result* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (!rc) rc = first_batch_init_locked(c);
+    if (rc) return rc;
+    const bool rank_major = first_batch_rank_major();
+    BatchPending pend;
+    mh::BatchTables t;
+    for (int p = 0; p < passes && !rc; ++p) {
+        mh::build_batch_tables(reqs, items, p, &t);
+        rc = first_batch_run_pass(c, reqs, src, t, slot_cap, rank_major, &pend, out);
+    }
+    if (!rc) rc = first_batch_drain(c, reqs, src, &pend, out);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -880,6 +1031,76 @@ int64_t mh_batch_plan(const mh_request* reqs, size_t n, mh_batch_item* out, int6
     for (const mh::BatchItem& it : items) {
         if (k >= cap) return cap + 1;  // cap + 1 signals truncation
         if (out) out[k] = mh_batch_item{it.req, it.first, it.count, it.kind, it.pass, it.slot, it.slots};
+        ++k;
+    }
+    return k;
+}
+
+int mh_search_first_batch(int dev, const mh_first_request* reqs, size_t n, mh_first_result* out) {
+    g_err.clear();
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+#ifdef MH_DEV_HOOKS
+    // as mh_search_first: the first-hit kernels have no variants of these hooks
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_first_batch does not support ") + hook);
+#endif
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    batch_requests(reqs, n, &status, &valid);
+    for (size_t i = 0; i < n; ++i) out[i] = mh_first_result{status[i], 0, 0, 0, 0};
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchItem> items;
+    mh::plan_batch(valid.data(), valid.size(), plan_opts(), slot_cap, &items);
+    int passes = 0;
+    for (const mh::BatchItem& it : items)
+        if (it.kind == 0) passes = std::max(passes, it.pass + 1);
+    if (passes) {
+        const int rc = first_batch_run_fused(dev, valid.data(), reqs, items, passes, slot_cap, out);
+        if (rc) return rc;
+    }
+    for (const mh::BatchItem& it : items) {  // the fallbacks, after the fused passes
+        if (it.kind != 1) continue;
+        const mh::BatchRequest& r = valid[it.idx];
+        mh_first f;
+        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, &f);
+        if (rc) return rc;
+        put_first_result(&out[r.id], f.hash, f.nonce, f.scanned, reqs[r.id].target);
+    }
+    return MH_OK;
+}
+
+int64_t mh_first_batch_order(const mh_request* reqs, size_t n, int32_t pass, uint32_t* out, int64_t cap) {
+    g_err.clear();
+    if (!reqs && n > 0) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> all;
+    batch_requests(reqs, n, &status, &all);
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])  // the first request mh_search would refuse, as mh_batch_plan
+            return fail(status[i], status[i] == MH_ERANGE ? "lower > upper"
+                                   : status[i] == MH_ETOOLONG ? "message longer than MH_MAX_MSG_LEN" : "msg is NULL");
+    std::vector<mh::BatchItem> items;
+    const uint32_t slot_cap = batch_slots();
+    mh::plan_batch(all.data(), n, plan_opts(), slot_cap, &items);
+    int passes = 0;
+    for (const mh::BatchItem& it : items)
+        if (it.kind == 0) passes = std::max(passes, it.pass + 1);
+    if (pass < 0 || pass >= passes) return fail(MH_EINVAL, "no such pass");
+    mh::BatchTables t;
+    mh::build_batch_tables(all.data(), items, pass, &t);
+    if (!mh::batch_tables_ok(t, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+    mh::FirstBatchTables ft;
+    mh::build_first_batch_tables(t, first_batch_rank_major(), &ft);
+    if (!mh::first_batch_tables_ok(t, ft)) return fail(MH_EINTERNAL, "internal: bad first-hit batch tables");
+    int64_t k = 0;
+    for (const uint32_t s : ft.order) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = s;
         ++k;
     }
     return k;

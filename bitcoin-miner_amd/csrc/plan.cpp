@@ -651,4 +651,50 @@ bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap) {
     return true;
 }
 
+// ---- batched first-hit search ----
+
+void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchTables* out) {
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    out->entry_req.assign(t.entries.size(), 0u);
+    size_t r = 0;
+    for (size_t ei = 0; ei < t.entries.size(); ++ei) {  // entries and segments are both in slot order
+        while (r + 1 < nreq && t.seg[r + 1] <= t.entries[ei].slot0) ++r;
+        out->entry_req[ei] = (uint32_t)r;
+    }
+    out->order.clear();
+    out->order.reserve(tiles);
+    if (!rank_major) {
+        for (size_t i = 0; i < tiles; ++i) out->order.push_back((uint32_t)i);
+        return;
+    }
+    // the requests that still have a tile of the current rank, in request order: each round emits
+    // one tile per such request, so the whole costs O(tiles + requests)
+    std::vector<uint32_t> active(nreq);
+    for (size_t i = 0; i < nreq; ++i) active[i] = (uint32_t)i;
+    for (uint32_t rank = 0; !active.empty(); ++rank) {
+        size_t keep = 0;
+        for (const uint32_t q : active) {
+            const uint32_t slot = t.seg[q] + rank;  // < seg[q + 1]: q is active
+            out->order.push_back(slot);
+            if (slot + 1u < t.seg[q + 1]) active[keep++] = q;
+        }
+        active.resize(keep);
+    }
+}
+
+bool first_batch_tables_ok(const BatchTables& t, const FirstBatchTables& f) {
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    if (f.entry_req.size() != t.entries.size() || f.order.size() != tiles || t.seg.size() != nreq + 1u) return false;
+    for (size_t ei = 0; ei < t.entries.size(); ++ei) {
+        const uint32_t r = f.entry_req[ei];
+        if (r >= nreq || t.entries[ei].slot0 < t.seg[r] || t.entries[ei].slot0 >= t.seg[r + 1]) return false;
+    }
+    std::vector<bool> seen(tiles, false);
+    for (const uint32_t s : f.order) {
+        if (s >= tiles || seen[s]) return false;
+        seen[s] = true;
+    }
+    return true;  // tiles distinct values below tiles: a permutation
+}
+
 }  // namespace mh

@@ -201,4 +201,21 @@ void build_batch_tables(const BatchRequest* reqs, const std::vector<BatchItem>& 
 // non-empty and together all slots.
 bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap);
 
+// ---- batched first-hit search (mh_search_first_batch / mh_first_batch_order) ----
+// The tables batch_scan_first reads beside a pass's BatchTables (the plan does not depend on the
+// targets, so plan_batch and build_batch_tables serve unchanged).
+struct FirstBatchTables {
+    std::vector<uint32_t> entry_req;  // per entry: its request of the pass (index into seg / req_idx)
+    std::vector<uint32_t> order;      // per workgroup: the tile (= partial slot) it runs
+};
+// rank_major: tile 0 of every request of the pass in request order, then tile 1 of every request
+// that has one, and so on -- a request's rank counts across its entries in nonce order, i.e. along
+// its slot segment -- so that a pass of many requests hashes each request's lowest nonces first;
+// otherwise the identity (request-major) order.
+void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchTables* out);
+
+// Checked before every launch, after batch_tables_ok(t): every entry's request is the one whose
+// segment holds the entry's slots, and order is a permutation of the pass's tiles.
+bool first_batch_tables_ok(const BatchTables& t, const FirstBatchTables& f);
+
 }  // namespace mh

@@ -25,6 +25,10 @@
 //                         second embedded code object, loaded by the first such search.
 //   generic_scan_first    generic_scan for mh_search_first.
 //   finish_first          one thread: the winning key back into its hash, the result out.
+//   batch_scan_first      batch_scan for mh_search_first_batch: first-hit keys, per-request device
+//                         words, tiles dispatched in the host's rank-major order.
+//   merge_segments_first  merge_segments, then the winning key back into its hash and the
+//                         request's {hash, nonce, scanned} out.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -227,8 +231,12 @@ namespace dev {
 // the tail image, the one- or two-block choice and the length words are made once; only the last
 // digit's byte changes.  With two tail blocks and the last digit in the second, block 0 is
 // compressed once for the ten.
-__device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32_t jlo, uint32_t jhi, uint64_t& bh,
-                                            uint64_t& bn) {
+// FIRST: the first-hit key (batch_scan_first): a hash <= target counts as 0, so the fold keeps the
+// smallest qualifying nonce; no test hooks there (mh_search_first_batch refuses them).  Without
+// FIRST, target is unused and the function is batch_scan's as before.
+template <bool FIRST>
+__device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32_t jlo, uint32_t jhi, uint64_t target,
+                                            uint64_t& bh, uint64_t& bn) {
     // digits of u; u <= (2^64 - 1) / 10 has at most 19
     constexpr uint64_t P10[19] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
                                   100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull,
@@ -306,10 +314,16 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
         uint32_t h0, h1;
         sha256_block_h01(s, x, h0, h1);
 #ifdef MH_DEV_HOOKS  // hash-XOR and coarse-hash test hooks, as in generic_scan
-        h0 = (h0 ^ mh_dev_hash_xor[0]) & keep_mask0(a.pad);
-        h1 = (h1 ^ mh_dev_hash_xor[1]) & keep_mask1(a.pad);
+        if constexpr (!FIRST) {
+            h0 = (h0 ^ mh_dev_hash_xor[0]) & keep_mask0(a.pad);
+            h1 = (h1 ^ mh_dev_hash_xor[1]) & keep_mask1(a.pad);
+        }
 #endif
-        const uint64_t hash = ((uint64_t)h0 << 32) | h1, n = n0 + j;
+        uint64_t hash = ((uint64_t)h0 << 32) | h1;
+        const uint64_t n = n0 + j;
+        if constexpr (FIRST) {
+            if (hash <= target) hash = 0ull;
+        }
         if (lex_less(hash, n, bh, bn)) {
             bh = hash;
             bn = n;
@@ -343,11 +357,71 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan(const BatchEntry* __
         const uint64_t off = base + (uint32_t)k * (uint32_t)kBlockThreads + threadIdx.x;
         if (off < nd) {
             const uint64_t u = u_first + off;
-            scan_decade(a, u, off == 0u ? j_first : 0u, u == u_last ? j_last : 9u, bh, bn);
+            scan_decade<false>(a, u, off == 0u ? j_first : 0u, u == u_last ? j_last : 9u, 0ull, bh, bn);
         }
     }
     block_min(bh, bn);
     if (threadIdx.x == 0) partials[blockIdx.x] = Partial{bh, bn};
+}
+
+// batch_scan for mh_search_first_batch: workgroup b runs tile order[b] -- the host's
+// rank-major dispatch order, a permutation of the pass's tiles -- with first-hit keys, and writes
+// partials[order[b]], so slots and segments keep batch_scan's layout.  The tile's request
+// (entry_req[entry]) has three device words (layout.hpp BatchFirstWords).  Thread 0 reads the
+// request's `first` word once before any hashing; the tile is skipped -- it writes the sentinel --
+// only when its smallest in-range nonce is larger than that word.  The word only decreases and
+// always holds a qualifying nonce of the request's range, so the tile of the smallest one, and
+// every tile with a smaller nonce, runs whatever value the read returns.  A tile that ran lowers
+// the word if it found a hit and adds its valid nonces to `scanned`.  No workgroup waits for
+// another: the grid always drains.  No test hooks.
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEntry* __restrict__ entries,
+                                                                  const uint32_t* __restrict__ tile_entry,
+                                                                  const uint32_t* __restrict__ entry_req,
+                                                                  const uint32_t* __restrict__ order,
+                                                                  BatchFirstWords* words,
+                                                                  Partial* __restrict__ partials) {
+    using namespace dev;
+    __shared__ uint32_t s_skip;
+    const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[blockIdx.x]);
+    const uint32_t ei = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_entry[tile]);
+    const uint32_t ri = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry_req[ei]);
+    const BatchEntry& e = entries[ei];
+    const GenArgs& a = e.g;
+    BatchFirstWords* w = words + ri;
+    const uint64_t first = a.first, lastn = a.first + (a.count - 1u);
+    const uint64_t u_first = first / 10u, u_last = lastn / 10u;
+    const uint32_t j_first = (uint32_t)(first - u_first * 10u), j_last = (uint32_t)(lastn - u_last * 10u);
+    const uint64_t nd = u_last - u_first + 1u;
+    const uint64_t base = (uint64_t)(tile - e.tile0) * kBatchTileDecades;  // < nd (the host's table check)
+    // the tile's decades d_lo .. d_hi and its nonces n_lo .. n_hi, ragged at the entry's two ends;
+    // (u_first + base) * 10 <= lastn, and d_hi * 10 + 9 is formed only below the entry's last decade
+    const uint64_t d_lo = u_first + base;
+    const uint64_t d_hi = nd - base > (uint64_t)kBatchTileDecades ? d_lo + (kBatchTileDecades - 1u) : u_last;
+    const uint64_t n_lo = base == 0u ? first : d_lo * 10u;  // the tile's smallest in-range nonce
+    const uint64_t n_hi = d_hi == u_last ? lastn : d_hi * 10u + 9u;
+    if (threadIdx.x == 0)
+        s_skip = n_lo > __hip_atomic_load(&w->first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
+    __syncthreads();
+    if (s_skip) {  // one value per workgroup
+        if (threadIdx.x == 0) partials[tile] = Partial{~0ull, ~0ull};
+        return;
+    }
+    const uint64_t target = w->target;  // never written on the device
+    uint64_t bh = ~0ull, bn = ~0ull;
+#pragma unroll 1
+    for (int k = 0; k < kBatchDecades; ++k) {
+        const uint64_t off = base + (uint32_t)k * (uint32_t)kBlockThreads + threadIdx.x;
+        if (off < nd) {
+            const uint64_t u = u_first + off;
+            scan_decade<true>(a, u, off == 0u ? j_first : 0u, u == u_last ? j_last : 9u, target, bh, bn);
+        }
+    }
+    block_min(bh, bn);
+    if (threadIdx.x == 0) {
+        partials[tile] = Partial{bh, bn};
+        if (bh == 0ull) atomicMin(&w->first, (unsigned long long)bn);
+        atomicAdd(&w->scanned, (unsigned long long)(n_hi - n_lo + 1u));
+    }
 }
 
 // One workgroup per request of the pass: results[r] = the lexicographic minimum of
@@ -369,6 +443,39 @@ __global__ __launch_bounds__(kBlockThreads) void merge_segments(const Partial* _
     }
     block_min(h, n);
     if (threadIdx.x == 0) results[r] = Partial{h, n};
+}
+
+// merge_segments for mh_search_first_batch: the same fold, then thread 0 turns a winning key 0
+// (some nonce of the request qualified; n is the smallest) back into that nonce's hash -- with the
+// GenArgs of the request's first entry: mid, tail, plen and t are per message -- and writes
+// results[r] = {hash, nonce, the request's scanned count}.
+__global__ __launch_bounds__(kBlockThreads) void merge_segments_first(const Partial* __restrict__ partials,
+                                                                      const uint32_t* __restrict__ seg,
+                                                                      const BatchEntry* __restrict__ entries,
+                                                                      const uint32_t* __restrict__ tile_entry,
+                                                                      const BatchFirstWords* __restrict__ words,
+                                                                      BatchFirstResult* __restrict__ results) {
+    using namespace dev;
+    const uint32_t r = blockIdx.x;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r]);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r + 1]);
+    uint64_t h = ~0ull, n = ~0ull;
+    for (uint32_t i = a + threadIdx.x; i < b; i += kBlockThreads) {
+        const Partial x = partials[i];
+        if (lex_less(x.hash, x.nonce, h, n)) {
+            h = x.hash;
+            n = x.nonce;
+        }
+    }
+    block_min(h, n);
+    if (threadIdx.x == 0) {
+        if (h == 0ull) {  // only a qualifying nonce has key 0 (the sentinel's is all ones)
+            uint32_t h0, h1;
+            hash_generic(entries[tile_entry[a]].g, n, h0, h1);
+            h = ((uint64_t)h0 << 32) | h1;
+        }
+        results[r] = BatchFirstResult{h, n, words[r].scanned};
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -628,6 +735,24 @@ hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_ent
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
                                  hipStream_t s) {
     hipLaunchKernelGGL(merge_segments, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, results);
+    return hipGetLastError();
+}
+
+// One pass of a first-hit batch: tiles workgroups of batch_scan_first, then requests workgroups of
+// merge_segments_first (the caller has checked the tables and the order, minehip.cpp first_batch_run_pass).
+hipError_t launch_batch_scan_first(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
+                                   const uint32_t* order, BatchFirstWords* words, Partial* partials, uint32_t tiles,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(batch_scan_first, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req, order,
+                       words, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_segments_first(const Partial* partials, const uint32_t* seg, const BatchEntry* entries,
+                                       const uint32_t* tile_entry, const BatchFirstWords* words,
+                                       BatchFirstResult* results, uint32_t requests, hipStream_t s) {
+    hipLaunchKernelGGL(merge_segments_first, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, entries,
+                       tile_entry, words, results);
     return hipGetLastError();
 }
 

@@ -10,6 +10,8 @@ tests read like the reference (line numbers into the reference repo):
   search_batch(requests)     many small scans fused into one GPU pass
   search_first(msg, lower, upper, target)
                              the smallest nonce whose hash is <= target
+  search_first_batch(requests)
+                             many small first-hit searches fused into one GPU pass
   miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
@@ -25,6 +27,7 @@ from ._lib import lib, mh_piece, mh_message, mh_kernel_stat, mh_span, OPS_PER_BL
 from ._lib import MH_OK, MH_EINVAL, MH_ERANGE, MH_ETOOLONG, MH_ENODEV, MH_EHIP  # noqa: F401
 from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
 from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
+from ._lib import mh_first_request, mh_first_result  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -137,6 +140,57 @@ def batch_plan(requests, cap=1 << 16):
     if k > cap:
         raise ValueError("batch plan longer than cap")
     return [{f: getattr(buf[i], f) for f, _ in mh_batch_item._fields_} for i in range(k)]
+
+
+def search_first_batch(requests, dev=0, errors="raise"):
+    """[(found, hash, nonce, scanned), ...] of many (msg, lower, upper, target) requests: found,
+    hash and nonce exactly what search_first() gives for each, with the small ones fused into one
+    GPU pass (mh_search_first_batch).  Per-request failures as search_batch: raised with the
+    request's index, or with errors="return" left in place in the list."""
+    if errors not in ("raise", "return"):
+        raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
+    requests = list(requests)
+    keep = []
+    arr = (mh_first_request * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        try:
+            msg, lower, upper, target = r
+        except (TypeError, ValueError):
+            raise ValueError(f"request {i}: expected (msg, lower, upper, target), got {r!r}") from None
+        for name, v in (("lower", lower), ("upper", upper), ("target", target)):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U64_MAX:
+                raise ValueError(f"request {i}: {name} = {v!r} is not a uint64")
+        m = _b(msg)
+        keep.append(m)
+        arr[i].msg, arr[i].len, arr[i].lower, arr[i].upper, arr[i].target = m, len(m), lower, upper, target
+    out = (mh_first_result * max(1, len(requests)))()
+    _check(lib.mh_search_first_batch(dev, arr, len(requests), out))
+    res = []
+    for i in range(len(requests)):
+        if out[i].status == MH_OK:
+            res.append((bool(out[i].found), out[i].hash, out[i].nonce, out[i].scanned))
+            continue
+        e = MinehipError(out[i].status, f"request {i}: {_REQUEST_ERRORS.get(out[i].status, 'failed')}")
+        e.index = i
+        if errors == "raise":
+            raise e
+        res.append(e)
+    return res
+
+
+def first_batch_order(requests, pass_=0, cap=1 << 18):
+    """Host-only: the dispatch order of pass `pass_` of search_first_batch over (msg, lower, upper)
+    requests (a target, if given, is ignored): entry b is the partial slot of the tile that
+    workgroup b runs (mh_first_batch_order)."""
+    requests = [tuple(r)[:3] for r in requests]
+    arr, keep = _requests(requests)
+    buf = (ctypes.c_uint32 * cap)()
+    k = lib.mh_first_batch_order(arr, len(requests), pass_, buf, cap)
+    if k < 0:
+        _check(k)
+    if k > cap:
+        raise ValueError("order longer than cap")
+    return list(buf[:k])
 
 
 def hash_batch(msg, nonces, dev=0):

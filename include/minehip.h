@@ -149,10 +149,46 @@ typedef struct mh_first {
  * target == 2^64-1 makes every nonce qualify (the answer is lower); target == 0 only a zero hash.
  * Errors and calling conventions as mh_search: MH_ERANGE, MH_ETOOLONG, MH_EINVAL (out == NULL
  * too), MH_ENODEV.  Additive in ABI 5 (no existing struct changes).
- * Out of scope: a multi-device form, a batched form, and the LSP protocol, which stays as it is
- * (the reference's Message has no target field). */
+ * Out of scope: a multi-device form, and the LSP protocol, which stays as it is (the reference's
+ * Message has no target field).  The batched form is mh_search_first_batch below. */
 int mh_search_first(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                     uint64_t target, mh_first *out);
+
+/* ---- batched first-hit search: many small proof-of-work questions at once ---- */
+
+typedef struct mh_first_request {
+    const uint8_t *msg;
+    size_t len;
+    uint64_t lower, upper, target;
+} mh_first_request; /* 40 bytes */
+
+typedef struct mh_first_result {
+    int32_t status, found;        /* status: MH_OK, or the MH_E* of this request alone */
+    uint64_t hash, nonce, scanned; /* valid when status == MH_OK */
+} mh_first_result; /* 32 bytes */
+
+/* out[i] = what mh_search_first(dev, reqs[i].msg, ..., reqs[i].target) gives, for n requests at
+ * once.  For a request whose status is MH_OK, found, hash and nonce are exactly mh_search_first's:
+ * the smallest nonce of the range with Hash <= target and its hash (found = 1), or, when nothing
+ * qualifies, mh_search's result with found = 0 and scanned = upper - lower + 1.  When something
+ * qualifies, nonce - lower + 1 <= scanned <= upper - lower + 1.  found, hash and nonce never
+ * depend on timing, pass packing, dispatch order or the fused / fallback split; only scanned does.
+ * Fused or fallback is decided as in mh_search_batch (the plan does not depend on the targets:
+ * mh_batch_plan shows it): the fused requests run as 2,560-nonce tiles of one launch of the
+ * batch_scan_first kernel per pass, one segmented merge and one copy-back per pass, one host
+ * synchronise for the call; a fallback request runs through the mh_search_first path after the
+ * fused passes.  Inside a pass the tiles are dispatched rank-major -- tile 0 of every request,
+ * then tile 1 of every request that has one, and so on (mh_first_batch_order) -- so that each
+ * request's lowest nonces are hashed first and a tile that starts after a smaller hit of its
+ * request was reported is skipped.  A tile that has started runs to its end: there is no check
+ * inside a tile, and no lane stops at its first hit.  MINEHIP_FIRST_BATCH_ORDER=request (read per
+ * call) keeps the request-major order instead.
+ * Per-request failures (MH_ERANGE, MH_ETOOLONG, MH_EINVAL for msg NULL with len > 0) go to
+ * out[i].status and do not stop the others; n == 0 returns MH_OK without touching a device; NULL
+ * arrays with n > 0 return MH_EINVAL; a device-level failure is the call's return code and leaves
+ * out undefined.  Results are in request order.  One device only; no multi-device form, no fused
+ * fast pieces, nothing in the LSP protocol or the miner.  Additive in ABI 5. */
+int mh_search_first_batch(int dev, const mh_first_request *reqs, size_t n, mh_first_result *out);
 
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
@@ -284,6 +320,14 @@ typedef struct mh_batch_item {
  * are more than cap (the first cap written, as mh_plan), or the MH_E* of the first request
  * mh_search would refuse.  n == 0 returns 0. */
 int64_t mh_batch_plan(const mh_request *reqs, size_t n, mh_batch_item *out, int64_t cap);
+
+/* Host only: the dispatch order of pass `pass` of mh_search_first_batch over reqs[0..n) (the plan
+ * is mh_batch_plan's; the targets play no part): out[b] is the partial slot of the tile that
+ * workgroup b of batch_scan_first runs, a permutation of the pass's slots.  Rank-major unless
+ * MINEHIP_FIRST_BATCH_ORDER=request; honours MINEHIP_BATCH_SLOTS.  Returns the pass's tile count,
+ * cap + 1 when there are more than cap (the first cap written, as mh_plan), the MH_E* of the
+ * first request mh_search would refuse, or MH_EINVAL when the plan has no such pass. */
+int64_t mh_first_batch_order(const mh_request *reqs, size_t n, int32_t pass, uint32_t *out, int64_t cap);
 
 /* One span of mh_search_multi's adaptive split (chunk == 0), ABI 4. */
 typedef struct mh_span {
