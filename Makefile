@@ -24,10 +24,13 @@ FASTFLAGS ?=
 # the code objects built from fast_search.hip, every one through the same passes: the product's
 # (embedded in the library), the coarse-hash test variant (-DMH_HASH_KEEP) and the
 # first-hit kernels first_scan<J, MODE> of mh_search_first (-DMH_FIRST; embedded too)
-FAST_NAMES := fast_search fast_search_keep fast_first
+# and the hits kernels hits_scan<J, MODE> of mh_search_hits (-DMH_HITS; embedded too)
+FAST_NAMES := fast_search fast_search_keep fast_first fast_hits
 FASTFLAGS_fast_search_keep := -DMH_HASH_KEEP
 FASTFLAGS_fast_first := -DMH_FIRST
+FASTFLAGS_fast_hits := -DMH_HITS
 FIRST_CO := $(BUILD)/fast_first.hsaco
+HITS_CO := $(BUILD)/fast_hits.hsaco
 
 LSPLIB  := $(PKG)/minehip/liblsp440.so
 APPS    := $(CSRC)/apps
@@ -74,9 +77,10 @@ $(ADD3_STAMP):
 	touch $@
 $(FAST_NAMES:%=$(BUILD)/%_split.s): $(BUILD)/%_split.s: $(BUILD)/%.s $(CSRC)/add3_split.py $(ADD3_STAMP)
 	python3 $(CSRC)/add3_split.py $(ADD3_SPLIT) $< $@ $(ADD3_LIKE_$*)
-# the first-hit build splits its per-nonce loops as the product's are split (add3_split.py, like_split.s)
+# the first-hit and hits builds split their per-nonce loops as the product's are split (add3_split.py, like_split.s)
 ADD3_LIKE_fast_first := $(FAST_SP)
-$(BUILD)/fast_first_split.s: $(FAST_SP) $(CSRC)/loop_mix.py
+ADD3_LIKE_fast_hits := $(FAST_SP)
+$(BUILD)/fast_first_split.s $(BUILD)/fast_hits_split.s: $(FAST_SP) $(CSRC)/loop_mix.py
 $(FAST_NAMES:%=$(BUILD)/%_prio.s): $(BUILD)/%_prio.s: $(BUILD)/%_split.s $(CSRC)/issue_prio.py $(CSRC)/valu_rates.py
 	python3 $(CSRC)/issue_prio.py $< $@
 $(FAST_MIX): $(FAST_PS) $(CSRC)/loop_mix.py $(CSRC)/valu_rates.py
@@ -91,7 +95,7 @@ $(BUILD)/fast_search_nomarker.hsaco: $(FAST_PS)
 	grep -v mh_fast_queue_args $< > $(BUILD)/fast_search_nomarker.s
 	$(LLVM)/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=$(ARCH) -c -o $(BUILD)/fast_search_nomarker.o $(BUILD)/fast_search_nomarker.s
 	$(LLVM)/ld.lld -shared -o $@ $(BUILD)/fast_search_nomarker.o
-$(FAST_O): $(CSRC)/fast_co.S $(FAST_CO) $(FIRST_CO)
+$(FAST_O): $(CSRC)/fast_co.S $(FAST_CO) $(FIRST_CO) $(HITS_CO)
 	gcc -c -fPIC -Wa,-I,$(BUILD) -o $@ $<
 
 # native C++ callers of the C-ABI (rpath: the library next to the package)

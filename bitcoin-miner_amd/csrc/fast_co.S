@@ -3,7 +3,9 @@
    libminehip.so.  search_kernels.hip loads it per device (hipModuleLoadData).
    Next to it, as a blob of its own, the first-hit kernels of mh_search_first
    (the same source with -DMH_FIRST through the same passes,
-   build/fast_first.hsaco), loaded per device by the first mh_search_first. */
+   build/fast_first.hsaco), loaded per device by the first mh_search_first,
+   and the hits kernels of mh_search_hits (-DMH_HITS, build/fast_hits.hsaco),
+   loaded per device by the first mh_search_hits. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -21,4 +23,12 @@ mh_first_co_begin:
     .globl mh_first_co_end
 mh_first_co_end:
     .size mh_first_co_begin, mh_first_co_end - mh_first_co_begin
+    .p2align 12
+    .globl mh_hits_co_begin
+    .type mh_hits_co_begin, @object
+mh_hits_co_begin:
+    .incbin "fast_hits.hsaco"
+    .globl mh_hits_co_end
+mh_hits_co_end:
+    .size mh_hits_co_begin, mh_hits_co_end - mh_hits_co_begin
     .section .note.GNU-stack,"",@progbits

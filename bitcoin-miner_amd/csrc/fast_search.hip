@@ -20,6 +20,8 @@
 // build's MINEHIP_DEV_CODE_OBJECT hook ever loads.  -DMH_FIRST builds the first-hit kernels
 // first_scan<J, MODE> (build/fast_first.hsaco, through the same passes), embedded as a
 // second code object that mh_search_first loads; without it nothing below differs from before.
+// -DMH_HITS builds the hits kernels hits_scan<J, MODE> (build/fast_hits.hsaco, through the same
+// passes), a third embedded code object that mh_search_hits loads; likewise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -179,6 +181,19 @@ struct FirstKernArgs {
 // branch and the chunk's end only).
 __device__ __forceinline__ const FirstArgs& first_args(const FastArgs& a) {
     return ((const FirstKernArgs*)&a)->f;
+}
+#endif
+#ifdef MH_HITS
+// The parameters of hits_scan<J, MODE> (below) as the kernarg segment holds them.
+struct HitsKernArgs {
+    FastArgs a;
+    Partial* partials;
+    HitsArgs h;
+};
+// The hits parameters of the kernel whose FastArgs `a` is: they follow it in the kernarg segment,
+// so the chunk body reads them through the pointer it already holds.
+__device__ __forceinline__ const HitsArgs& hits_args(const FastArgs& a) {
+    return ((const HitsKernArgs*)&a)->h;
 }
 #endif
 template <int J, int MODE>
@@ -400,7 +415,19 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
 #endif
             // New wave best (rare): a uniform branch, so H1 and the
             // lexicographic compare cost nothing on the common path.
+#ifdef MH_HITS
+            // Hits variant: a lane is a candidate when its H0 <= max(wave best H0, target >> 32),
+            // which admits what the product admits and every possible hit (a hit has H0 <= target >> 32)
+            // (a scalar load per nonce through a laundered pointer: kept in an SGPR across the
+            // loop, the word costs the TwoEarly layout's loop two VALU instructions)
+            using KHits = __attribute__((address_space(4))) const HitsKernArgs;
+            KHits* kh = (KHits*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kh));
+            const uint32_t hits_thi = (uint32_t)(kh->h.target >> 32);
+            uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= (wbh0 > hits_thi ? wbh0 : hits_thi)) & valid_mask;
+#else
             uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= wbh0) & valid_mask;  // MH_FIRST: h0 <= lim
+#endif
             if (__builtin_expect(cm != 0ull, 0)) {
 #ifdef MH_HASH_KEEP
                 const uint32_t h1 = ((st[1] + a63) ^ xor1) & keep1;
@@ -408,6 +435,42 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 const uint32_t h1 = st[1] + a63;
 #endif
                 const uint32_t q = g * 10u + i;
+#ifdef MH_HITS
+                // The hits of this step (valid lanes only: cm holds no other): the lowest hit lane
+                // takes one slot per hit from the cursor with one atomic add, the base comes back
+                // to every lane through readlane, and the hits go to base + rank in lane order,
+                // one uniform {hash, nonce} at a time stored by that lane -- the scalar walk of
+                // the candidate loop below, so no lane does 64-bit nonce arithmetic.  The cursor
+                // advances for every hit, also past the buffer's end, where nothing is stored.
+                {
+                    const HitsArgs& ha = hits_args(a);
+                    const uint32_t thi = (uint32_t)(ha.target >> 32), tlo = (uint32_t)ha.target;
+                    uint64_t hm = __builtin_amdgcn_ballot_w64(h0 < thi || (h0 == thi && h1 <= tlo)) & cm;
+                    if (hm) {
+                        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                        const uint32_t lead = (uint32_t)__builtin_ctzll(hm);
+                        unsigned long long taken = 0ull;
+                        if (lane == lead) taken = atomicAdd(ha.cursor, (unsigned long long)__builtin_popcountll(hm));
+                        uint64_t slot =
+                            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(taken >> 32), (int)lead) << 32) |
+                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)taken, (int)lead);
+                        do {
+                            const uint32_t l = (uint32_t)__builtin_ctzll(hm);
+                            hm &= hm - 1ull;
+                            const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)h0, (int)l);
+                            const uint32_t c1 = (uint32_t)__builtin_amdgcn_readlane((int)h1, (int)l);
+                            uint64_t cn;
+                            if constexpr (!EARLY)
+                                cn = (wave_u0 + l) * a.pow10L + q;
+                            else
+                                cn = spread(wave_u0 + l, a.hole, a.hole_w) * a.u_mul + spread(g, a.g_hole, 1u) * a.g_mul +
+                                     i * a.i_mul;
+                            if (slot < ha.cap && lane == lead) ha.hits[slot] = Hit{((uint64_t)c0 << 32) | c1, cn};
+                            ++slot;
+                        } while (hm);
+                    }
+                }
+#endif
 #ifdef MH_FIRST
                 // The hits of this step: all take key 0, and the lowest lane holds the smallest
                 // nonce of them (at one (g, i) the nonce grows with the lane: spread is monotonic),
@@ -505,8 +568,17 @@ __device__ __forceinline__ uint32_t claim_chunk(uint32_t* counter) {
 
 #ifndef MH_FIRST
 template <int J, int MODE>
+#ifdef MH_HITS
+// hits_scan<J, MODE>: fast_search with the append of every hit in its chunk body, for
+// mh_search_hits.  The launch forms are fast_search's own, and no chunk is ever skipped: the count
+// needs every nonce.  HitsArgs is read through the kernarg segment (hits_args above).
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void hits_scan(const FastArgs a,
+                                                                         Partial* __restrict__ partials,
+                                                                         const HitsArgs) {
+#else
 __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void fast_search(const FastArgs a,
                                                                            Partial* __restrict__ partials) {
+#endif
     // Static: workgroup b runs chunk b.  Work queue (a.counter set, grid <= the resident
     // workgroups): each workgroup claims chunks until the counter passes n_chunks; every
     // workgroup leaves once a claim comes back >= n_chunks, so the grid always drains.
@@ -629,7 +701,12 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 // costs less with the digit ending word J innermost than with the last digit
 // in word J + 1 (plan.cpp: nonce_cost(J) < nonce_cost(J + 1)).
 #ifndef MH_FIRST
+#ifdef MH_HITS
+#define MH_INST(j, m) \
+    template __global__ void hits_scan<j, m>(const FastArgs, Partial* __restrict__, const HitsArgs);
+#else
 #define MH_INST(j, m) template __global__ void fast_search<j, m>(const FastArgs, Partial* __restrict__);
+#endif
 #else
 #define MH_INST(j, m) \
     template __global__ void first_scan<j, m>(const FastArgs, Partial* __restrict__, const FirstArgs);

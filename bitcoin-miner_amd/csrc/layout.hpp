@@ -149,6 +149,25 @@ struct FirstArgs {
     unsigned long long* scanned;  // valid nonces of the chunks / workgroups that were not skipped
 };
 
+// ---- every hit (mh_search_hits) ----
+// One qualifying nonce as the hits kernels append it and the host returns it (mh_hit).
+struct Hit {
+    uint64_t hash;
+    uint64_t nonce;
+};
+
+// Extra kernel parameters of the hits kernels (hits_scan<J, MODE> of the build/fast_hits.hsaco
+// code object, generic_scan_hits), after the product kernels' own two.  Every nonce of the range
+// with Hash <= target takes one slot from *cursor -- a wave takes the slots of its step's hits
+// with one atomic add -- and its {hash, nonce} goes to hits[slot] if slot < cap.  The cursor
+// advances for every hit, stored or not, so its final value is the exact count.
+struct HitsArgs {
+    uint64_t target;
+    unsigned long long* cursor;  // hits so far (zeroed by the host before the scan)
+    Hit* hits;                   // cap entries, in the order the slots were taken
+    uint64_t cap;
+};
+
 // ---- batched search (batch_scan / merge_segments) ----
 // Many small Requests in one launch.  A lane's unit of work is an aligned decade, the ten nonces
 // 10u .. 10u+9: they share their digit count, so u is formatted once for the ten.  A tile is one

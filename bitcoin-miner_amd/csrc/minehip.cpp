@@ -48,6 +48,10 @@ hipError_t launch_generic_scan_first(const GenArgs& a, Partial* partials, uint32
                                      hipStream_t s);
 hipError_t launch_finish_first(const GenArgs& a, const Partial* best, const unsigned long long* scanned, uint64_t* out,
                                hipStream_t s);
+hipError_t launch_fast_hits(int dev, int J, int mode, const FastArgs& a, Partial* partials, const HitsArgs& h,
+                            hipStream_t s);
+hipError_t launch_generic_scan_hits(const GenArgs& a, Partial* partials, uint32_t blocks, const HitsArgs& h,
+                                    hipStream_t s);
 hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials, uint32_t tiles,
                              hipStream_t s);
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
@@ -133,6 +137,11 @@ struct DevCtx {
     uint64_t* d_first = nullptr;  // [0] smallest qualifying nonce so far, [1] nonces scanned, [2..4] the result
     uint64_t* h_first = nullptr;  // pinned: hash, nonce, scanned
     const mh::FirstArgs* first = nullptr;  // set while an mh_search_first enqueues its pieces
+    // every hit (mh_search_hits), allocated by the first such call
+    mh::Hit* d_hits = nullptr;      // MH_HITS_MAX_CAP entries
+    uint64_t* d_hcursor = nullptr;  // hits of the scan in flight
+    uint64_t* h_hcursor = nullptr;  // pinned
+    const mh::HitsArgs* hits = nullptr;  // set while an mh_search_hits enqueues its pieces
 #ifdef MH_DEV_HOOKS
     uint32_t keep = 0;        // this call's coarse-hash word (MINEHIP_DEV_HASH_KEEP; 0: unset)
     bool keep_fast = false;   // ... and the fast code object in use is the variant that reads it
@@ -379,6 +388,11 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
             MH_HIP(mh::launch_fast_first(c->dev, p.J, p.mode, fa, out, *c->first, s));
         else
             MH_HIP(mh::launch_generic_scan_first(ga, out, blocks, *c->first, s));
+    } else if (c->hits) {  // mh_search_hits: the hits kernels over the same pieces
+        if (p.kind == 0)
+            MH_HIP(mh::launch_fast_hits(c->dev, p.J, p.mode, fa, out, *c->hits, s));
+        else
+            MH_HIP(mh::launch_generic_scan_hits(ga, out, blocks, *c->hits, s));
     } else if (p.kind == 0)
         MH_HIP(mh::launch_fast(c->dev, p.J, p.mode, fa, out, s));
     else
@@ -584,6 +598,135 @@ int search_first_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t u
     out->scanned = c->h_first[2];
     out->found = out->hash <= target ? 1 : 0;  // without a qualifying nonce the minimum itself is > target
     out->reserved = 0;
+    return MH_OK;
+}
+
+//   MINEHIP_HITS_SLOTS     entries of the device hit buffer one scan of mh_search_hits may fill
+//                          (1..MH_HITS_MAX_CAP, the default): a lower value makes a search with more
+//                          hits rebuild its list window by window (tests; the results never depend
+//                          on it)
+uint64_t hits_slots() {
+    if (const char* e = getenv("MINEHIP_HITS_SLOTS")) {
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (v >= 1 && v <= MH_HITS_MAX_CAP) return v;
+    }
+    return MH_HITS_MAX_CAP;
+}
+
+// One scan of [lower, upper] for mh_search_hits, under the device's lock: search_impl's plan,
+// streams, partial flushes and work-queue counters over the hits kernels (hits_scan<J, MODE>,
+// generic_scan_hits; layout.hpp HitsArgs), one synchronise, then the range's minimum in c->h_best,
+// its hit count in *count and, if `got` is given, the min(count, slots) entries the device buffer
+// holds in *got (in no particular order; all of the range's hits exactly if count <= slots).
+int hits_scan_range(DevCtx* c, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, uint64_t slots,
+                    uint64_t* count, std::vector<mh::Hit>* got) {
+    MH_HIP(hipMemsetAsync(c->d_best, 0xFF, sizeof(Partial), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_hcursor, 0, sizeof(uint64_t), c->stream));
+    const mh::PlanOpts opt = plan_opts();
+    if (opt.queue) MH_HIP(hipMemsetAsync(c->d_counters, 0, sizeof(uint32_t) * kQueueSlots, c->stream));
+    c->qoff = 0;
+    bool any_coarse = false, any_fine = false;
+    if (opt.streams == 2)
+        mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
+            (coarse_piece(p, opt) ? any_coarse : any_fine) = true;
+            return !(any_coarse && any_fine);
+        });
+    const bool split = opt.streams == 2 && any_coarse && any_fine;
+    if (split) {
+        const int rc = piece_streams_wait_main(c);
+        if (rc) return rc;
+    }
+    const mh::HitsArgs hargs{target, (unsigned long long*)c->d_hcursor, c->d_hits, slots};
+    int err = MH_OK;
+    c->poff = 0;
+    c->hits = &hargs;
+    mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
+        err = enqueue_piece(c, p, opt, split);
+        return err == MH_OK;
+    });
+    c->hits = nullptr;
+    if (!err) err = flush_partials(c, split);
+    if (err) {
+        for (auto ps : c->ps)
+            if (ps) (void)hipStreamSynchronize(ps);
+        (void)hipStreamSynchronize(c->stream);
+        return err;
+    }
+    MH_HIP(hipMemcpyAsync(c->h_best, c->d_best, sizeof(Partial), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_hcursor, c->d_hcursor, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        const int rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    *count = *c->h_hcursor;
+    if (got) {
+        got->resize((size_t)std::min(*count, slots));
+        if (!got->empty()) MH_HIP(hipMemcpy(got->data(), c->d_hits, got->size() * sizeof(mh::Hit), hipMemcpyDeviceToHost));
+    }
+    return MH_OK;
+}
+
+// mh_search_hits: one scan of the whole range gives the minimum, the exact count (the cursor
+// advances for every hit) and, while the count fits the device buffer, every hit; the host sorts
+// them by nonce and returns the first `cap`.  When the buffer overflowed, which entries it kept
+// depends on timing, so the list is rebuilt from `lower` upward out of windows [cur, cur + w - 1]
+// scanned by the same kernels: w is sized from the observed density for about a quarter of the
+// buffer per window, a window that overflows all the same is halved and scanned again (one of at
+// most `slots` nonces cannot overflow), one that fits is complete, so sorted and appended, until
+// min(count, cap) entries are collected.  The count and the minimum are the first scan's.
+int search_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, mh_hit* hits,
+                     size_t cap, mh_hits* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    if (!c->d_hits) MH_HIP(hipMalloc(&c->d_hits, sizeof(mh::Hit) * MH_HITS_MAX_CAP));
+    if (!c->d_hcursor) MH_HIP(hipMalloc(&c->d_hcursor, sizeof(uint64_t)));
+    if (!c->h_hcursor) MH_HIP(hipHostMalloc(&c->h_hcursor, sizeof(uint64_t), hipHostMallocDefault));
+#ifdef MH_DEV_HOOKS
+    c->keep = 0;  // mh_search_hits refused the hash hooks; nothing of an earlier search's stays
+    c->keep_fast = c->xor_on = c->xor_fast = false;
+#endif
+    const uint64_t slots = hits_slots();
+    std::vector<mh::Hit> got;
+    uint64_t count = 0;
+    rc = hits_scan_range(c, pre, lower, upper, target, slots, &count, cap ? &got : nullptr);
+    if (rc) return rc;
+    out->count = count;
+    out->stored = std::min<uint64_t>(count, cap);
+    out->hash = c->h_best->hash;
+    out->nonce = c->h_best->nonce;
+    const auto by_nonce = [](const mh::Hit& x, const mh::Hit& y) { return x.nonce < y.nonce; };
+    if (cap && count > slots) {  // the buffer dropped entries: rebuild the list window by window
+        const double total = (double)(upper - lower) + 1.0;
+        const double per_window = std::max(1.0, (double)slots / 4.0 * (total / (double)count));
+        uint64_t w = per_window >= 9.0e18 ? (uint64_t)9.0e18 : (uint64_t)per_window;
+        std::vector<mh::Hit> list, win;
+        uint64_t cur = lower;
+        while (list.size() < out->stored) {
+            const uint64_t hi = (upper - cur < w - 1u) ? upper : cur + (w - 1u);
+            uint64_t wc = 0;
+            rc = hits_scan_range(c, pre, cur, hi, target, slots, &wc, &win);
+            if (rc) return rc;
+            if (wc > slots) {  // hi - cur + 1 > slots >= 1 here
+                w = (hi - cur + 1u) / 2u;
+                continue;
+            }
+            std::sort(win.begin(), win.end(), by_nonce);
+            list.insert(list.end(), win.begin(), win.end());
+            if (hi == upper) break;
+            cur = hi + 1u;
+        }
+        if (list.size() < out->stored) return fail(MH_EINTERNAL, "internal: the hit windows hold fewer hits than the scan counted");
+        got.swap(list);
+    } else {
+        std::sort(got.begin(), got.end(), by_nonce);
+    }
+    for (uint64_t i = 0; i < out->stored; ++i) hits[i] = mh_hit{got[(size_t)i].hash, got[(size_t)i].nonce};
     return MH_OK;
 }
 
@@ -933,6 +1076,26 @@ int mh_search_first(int dev, const uint8_t* msg, size_t len, uint64_t lower, uin
     mh::Prefix pre;
     mh::absorb_prefix(msg, len, &pre);
     return search_first_impl(dev, pre, lower, upper, target, out);
+}
+
+int mh_search_hits(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                   mh_hit* hits, size_t cap, mh_hits* out) {
+    g_err.clear();
+    if (!out) return fail(MH_EINVAL, "NULL output pointer");
+    if (cap > MH_HITS_MAX_CAP) return fail(MH_EINVAL, "cap is larger than MH_HITS_MAX_CAP");
+    if (!hits && cap > 0) return fail(MH_EINVAL, "hits is NULL with cap > 0");
+    int rc = check_common(msg, len);
+    if (rc) return rc;
+    if (lower > upper) return fail(MH_ERANGE, "lower > upper");
+#ifdef MH_DEV_HOOKS
+    // the hits kernels have no variants of these hooks: refuse, never ignore them
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_hits does not support ") + hook);
+#endif
+    mh::Prefix pre;
+    mh::absorb_prefix(msg, len, &pre);
+    return search_hits_impl(dev, pre, lower, upper, target, hits, cap, out);
 }
 
 int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,

@@ -25,6 +25,10 @@
 //                         second embedded code object, loaded by the first such search.
 //   generic_scan_first    generic_scan for mh_search_first.
 //   finish_first          one thread: the winning key back into its hash, the result out.
+//   hits_scan<J, MODE>    (fast_search.hip, -DMH_HITS) fast_search for mh_search_hits: every nonce
+//                         whose hash is <= a target appended to a device buffer; a third embedded
+//                         code object, loaded by the first such search.
+//   generic_scan_hits     generic_scan for mh_search_hits.
 //   batch_scan_first      batch_scan for mh_search_first_batch: first-hit keys, per-request device
 //                         words, tiles dispatched in the host's rank-major order.
 //   merge_segments_first  merge_segments, then the winning key back into its hash and the
@@ -51,6 +55,8 @@
 extern "C" const unsigned char mh_fast_co_begin[];
 // the same source built with -DMH_FIRST: first_scan<J, MODE>, the fast kernels of mh_search_first
 extern "C" const unsigned char mh_first_co_begin[];
+// the same source built with -DMH_HITS: hits_scan<J, MODE>, the fast kernels of mh_search_hits
+extern "C" const unsigned char mh_hits_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -162,6 +168,40 @@ __global__ __launch_bounds__(kBlockThreads) void generic_scan_first(const GenArg
         if (hash == 0ull) atomicMin(f.first, (unsigned long long)nonce);
         atomicAdd(f.scanned, (unsigned long long)(left < (uint64_t)kBlockThreads ? left : (uint64_t)kBlockThreads));
     }
+}
+
+// generic_scan for mh_search_hits: the same minimum, and every thread below a.count
+// whose hash is <= h.target appends {hash, nonce} to the hit buffer.  Per wave, the lowest hit lane
+// takes one slot per hit from the cursor with one atomic add and hit number r of the wave (in lane
+// order) goes to base + r if that lies below the capacity; the cursor advances either way, so it
+// ends as the exact count.  No test hooks: mh_search_hits refuses them.
+__global__ __launch_bounds__(kBlockThreads) void generic_scan_hits(const GenArgs a, Partial* __restrict__ partials,
+                                                                   const HitsArgs h) {
+    using namespace dev;
+    const uint32_t gid = blockIdx.x * kBlockThreads + threadIdx.x;
+    const uint64_t n = a.first + gid;
+    uint32_t h0, h1;
+    hash_generic(a, n, h0, h1);
+    uint64_t hash = ((uint64_t)h0 << 32) | h1, nonce = n;
+    const bool hit = gid < a.count && hash <= h.target;
+    const uint64_t hm = __builtin_amdgcn_ballot_w64(hit);
+    if (hm) {  // one value per wave
+        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const uint32_t lead = (uint32_t)__builtin_ctzll(hm);
+        unsigned long long taken = 0ull;
+        if (lane == lead) taken = atomicAdd(h.cursor, (unsigned long long)__builtin_popcountll(hm));
+        const uint64_t base =
+            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(taken >> 32), (int)lead) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)taken, (int)lead);
+        const uint64_t slot = base + (uint32_t)__builtin_popcountll(hm & ((1ull << lane) - 1ull));
+        if (hit && slot < h.cap) h.hits[slot] = Hit{hash, nonce};
+    }
+    if (gid >= a.count) {
+        hash = ~0ull;
+        nonce = ~0ull;
+    }
+    block_min(hash, nonce);
+    if (threadIdx.x == 0) partials[blockIdx.x] = Partial{hash, nonce};
 }
 
 // The end of an mh_search_first, one thread on the main stream after the last merge: a winning
@@ -502,20 +542,25 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 
 // queue_ok: the code object carries fast_search.hip's mh_fast_queue_args marker at this
 // library's sizeof(FastArgs), i.e. its kernels claim chunks from a.counter
-// first: the first-hit kernels first_scan<J, MODE> of the second embedded code object (module key
-// ":first", no file of that name is ever loaded), which no hook replaces
-hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr, bool first = false) {
+// variant: kFastFirst, the first-hit kernels first_scan<J, MODE> of the second embedded code object
+// (module key ":first", no file of that name is ever loaded), or kFastHits, the hits kernels
+// hits_scan<J, MODE> of the third (":hits"); no hook replaces either
+enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2 };
+hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr,
+                         FastVariant variant = kFastProduct) {
+    const bool first = variant == kFastFirst, hits = variant == kFastHits;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
-    const std::string path = first ? ":first" : (co && *co) ? co : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : (co && *co) ? co : "";
 #else
-    const std::string path = first ? ":first" : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
     if (it == g_mods.end()) {
         hipModule_t m;
         const hipError_t e = first          ? hipModuleLoadData(&m, mh_first_co_begin)
+                             : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
                              : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
                                             : hipModuleLoad(&m, path.c_str());
         if (e != hipSuccess) {
@@ -546,8 +591,9 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
     if (fit == g_funcs.end()) {
         char name[96];
         snprintf(name, sizeof name,
-                 first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
-                       : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
+                 first  ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
+                 : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
+                        : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
                  J, mode);
         hipFunction_t fn;
         const hipError_t e = hipModuleGetFunction(&fn, it->second, name);
@@ -676,14 +722,15 @@ hipError_t launch_fast(int dev, int J, int mode, const FastArgs& a, Partial* par
     return hipModuleLaunchKernel(f, grid, 1, 1, kBlockThreads, 1, 1, lds, s, params, nullptr);
 }
 
-// launch_fast for mh_search_first: first_scan<J, mode> of the first-hit code object (loaded on dev,
-// the current device, by the first call), the same grid rule, f as the third kernel parameter.
-hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partial* partials, const FirstArgs& f,
-                             hipStream_t s) {
+// launch_fast for the kernels of another embedded code object (loaded on dev, the current device,
+// by the first call): the same grid rule, `extra` as the third kernel parameter.
+namespace {
+hipError_t launch_fast_variant(int dev, int J, int mode, const FastArgs& a, Partial* partials, FastVariant variant,
+                               void* extra, hipStream_t s) {
     if (!fast_variant_exists(J, mode)) return hipErrorInvalidValue;
     hipFunction_t fn;
     bool queue_ok = false;
-    hipError_t e = fast_function(dev, J, mode, &fn, &queue_ok, true);
+    hipError_t e = fast_function(dev, J, mode, &fn, &queue_ok, variant);
     if (e != hipSuccess) return e;
     FastArgs args = a;
     if (!queue_ok) args.counter = nullptr;
@@ -695,9 +742,29 @@ hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partia
         grid = std::min(grid, resident);
     }
     Partial* out = partials;
-    FirstArgs fa = f;
-    void* params[] = {&args, &out, &fa};
+    void* params[] = {&args, &out, extra};
     return hipModuleLaunchKernel(fn, grid, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+}  // namespace
+
+// mh_search_first: first_scan<J, mode> of the first-hit code object, f as the third kernel parameter.
+hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partial* partials, const FirstArgs& f,
+                             hipStream_t s) {
+    FirstArgs fa = f;
+    return launch_fast_variant(dev, J, mode, a, partials, kFastFirst, &fa, s);
+}
+
+// mh_search_hits: hits_scan<J, mode> of the hits code object, h as the third kernel parameter.
+hipError_t launch_fast_hits(int dev, int J, int mode, const FastArgs& a, Partial* partials, const HitsArgs& h,
+                            hipStream_t s) {
+    HitsArgs ha = h;
+    return launch_fast_variant(dev, J, mode, a, partials, kFastHits, &ha, s);
+}
+
+hipError_t launch_generic_scan_hits(const GenArgs& a, Partial* partials, uint32_t blocks, const HitsArgs& h,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL(generic_scan_hits, dim3(blocks), dim3(kBlockThreads), 0, s, a, partials, h);
+    return hipGetLastError();
 }
 
 hipError_t launch_generic_scan_first(const GenArgs& a, Partial* partials, uint32_t blocks, const FirstArgs& f,

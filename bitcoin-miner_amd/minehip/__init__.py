@@ -10,6 +10,8 @@ tests read like the reference (line numbers into the reference repo):
   search_batch(requests)     many small scans fused into one GPU pass
   search_first(msg, lower, upper, target)
                              the smallest nonce whose hash is <= target
+  search_hits(msg, lower, upper, target, cap=4096)
+                             every nonce whose hash is <= target, and how many there are
   search_first_batch(requests)
                              many small first-hit searches fused into one GPU pass
   miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
@@ -28,6 +30,7 @@ from ._lib import MH_OK, MH_EINVAL, MH_ERANGE, MH_ETOOLONG, MH_ENODEV, MH_EHIP  
 from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
 from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
 from ._lib import mh_first_request, mh_first_result  # noqa: F401
+from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -68,6 +71,19 @@ def search_first(msg, lower, upper, target, dev=0):
     out = mh_first()
     _check(lib.mh_search_first(dev, m, len(m), lower, upper, target, ctypes.byref(out)))
     return bool(out.found), out.hash, out.nonce, out.scanned
+
+
+def search_hits(msg, lower, upper, target, cap=4096, dev=0):
+    """(count, [(nonce, hash), ...], (min_hash, min_nonce)): how many nonces n of [lower, upper] have
+    Hash(msg, n) <= target, the min(count, cap) smallest of them in increasing order with their
+    hashes, and search()'s result for the range (mh_search_hits).  cap = 0 only counts."""
+    m = _b(msg)
+    if cap < 0 or cap > MH_HITS_MAX_CAP:
+        raise MinehipError(MH_EINVAL, f"cap must be 0..{MH_HITS_MAX_CAP}")
+    buf = (mh_hit * cap)() if cap else None
+    out = mh_hits()
+    _check(lib.mh_search_hits(dev, m, len(m), lower, upper, target, buf, cap, ctypes.byref(out)))
+    return out.count, [(buf[i].nonce, buf[i].hash) for i in range(out.stored)], (out.hash, out.nonce)
 
 
 def search_multi(msg, lower, upper, devs=None, chunk=0):

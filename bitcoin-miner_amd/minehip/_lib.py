@@ -27,6 +27,7 @@ MH_EREJECTED = -8
 OPS_PER_BLOCK = 1376  # MH_OPS_PER_BLOCK
 MH_ABI_VERSION = 5    # include/minehip.h: the struct layouts below are this version's
 MH_MAX_WORKERS = 256  # most devices one mh_search_multi / mh_multi_plan call may list
+MH_HITS_MAX_CAP = 1 << 20  # most entries one mh_search_hits call returns
 
 #: every symbol include/*.h declares
 EXPORTS = (
@@ -34,7 +35,7 @@ EXPORTS = (
     "mh_last_error", "mh_msg_encode", "mh_msg_decode", "mh_miner_handle",
     "mh_profile_enable", "mh_profile_read", "mh_profile_kernels", "mh_plan", "mh_multi_plan",
     "mh_multi_rates", "mh_search_batch", "mh_batch_plan", "mh_miner_handle_batch",
-    "mh_search_first", "mh_search_first_batch", "mh_first_batch_order",
+    "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -75,6 +76,15 @@ class mh_result(ctypes.Structure):
 class mh_first(ctypes.Structure):
     _fields_ = [("found", ctypes.c_int32), ("reserved", ctypes.c_int32), ("hash", ctypes.c_uint64),
                 ("nonce", ctypes.c_uint64), ("scanned", ctypes.c_uint64)]
+
+
+class mh_hit(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint64), ("nonce", ctypes.c_uint64)]
+
+
+class mh_hits(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64), ("stored", ctypes.c_uint64), ("hash", ctypes.c_uint64),
+                ("nonce", ctypes.c_uint64)]
 
 
 class mh_first_request(ctypes.Structure):
@@ -156,6 +166,8 @@ def _load():
     L.mh_multi_rates.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
     L.mh_search_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_result)]
     L.mh_search_first.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.POINTER(mh_first)]
+    L.mh_search_hits.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.POINTER(mh_hit), sz,
+                                 ctypes.POINTER(mh_hits)]
     L.mh_search_first_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_first_request), sz,
                                         ctypes.POINTER(mh_first_result)]
     L.mh_first_batch_order.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.c_int32,

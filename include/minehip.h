@@ -190,6 +190,39 @@ typedef struct mh_first_result {
  * fast pieces, nothing in the LSP protocol or the miner.  Additive in ABI 5. */
 int mh_search_first_batch(int dev, const mh_first_request *reqs, size_t n, mh_first_result *out);
 
+/* ---- every hit: all nonces of a range whose hash meets a target ---------- */
+
+#define MH_HITS_MAX_CAP (1u << 20) /* most entries one call returns */
+
+typedef struct mh_hit {
+    uint64_t hash, nonce;
+} mh_hit; /* 16 bytes */
+
+typedef struct mh_hits {
+    uint64_t count;       /* nonces of [lower, upper] with Hash <= target (mod 2^64) */
+    uint64_t stored;      /* entries written to hits: min(count, cap) */
+    uint64_t hash, nonce; /* exactly what mh_search returns for the range */
+} mh_hits; /* 32 bytes */
+
+/* Which nonces of [lower, upper] have Hash(msg, n) <= target, and how many -- the shares a pool
+ * collects, the sample a difficulty estimate needs.  out->count is the exact number of them,
+ * hits[0 .. out->stored) the stored = min(count, cap) SMALLEST of them in strictly increasing
+ * nonce order, each with its hash, and out->hash / out->nonce the range's minimum, whether or not
+ * anything qualifies.  cap == 0 with hits == NULL asks for the count (and the minimum) alone.
+ * The call hashes the whole range once, like mh_search: the scan kernels are mh_search's with an
+ * append of every hit to a device buffer, so there is no early end.  It is built for sparse
+ * targets; a loose one, where most wave steps hold a hit, is correct but slow (the hits of a wave
+ * step are appended one after the other).  The buffer holds MH_HITS_MAX_CAP entries
+ * (MINEHIP_HITS_SLOTS, read per call, lowers that for tests); with more hits than that and
+ * cap > 0, the list is rebuilt from `lower` upward by re-scanning windows of the range until
+ * `stored` entries are collected.  Nothing returned depends on the launch plan, the streams, the
+ * queue mode, the timing or the size of that buffer.
+ * Errors: MH_EINVAL for out == NULL, cap > MH_HITS_MAX_CAP, or hits == NULL with cap > 0;
+ * MH_ERANGE, MH_ETOOLONG, MH_ENODEV as mh_search.  One device only; no batched form, nothing in
+ * the LSP protocol.  Additive in ABI 5 (no existing struct changes). */
+int mh_search_hits(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
+                   uint64_t target, mh_hit *hits, size_t cap, mh_hits *out);
+
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
 
