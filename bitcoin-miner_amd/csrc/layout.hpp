@@ -204,4 +204,24 @@ struct BatchFirstResult {
     uint64_t hash, nonce, scanned;
 };
 
+// ---- batched hits (batch_scan_hits / merge_segments_hits) ----
+// The device words of one request of a pass of mh_search_hits_batch, in a table parallel to the
+// segments, found by a tile through entry_req[entry] as BatchFirstWords are.  Every nonce of the
+// request with Hash <= target takes one slot from `cursor`, and its {hash, nonce} goes to entry
+// offset + slot of the device hit buffer if slot < slots: the request's region, which the host
+// hands out and checks (plan.hpp HitsBatchTables).  The cursor advances for every hit, stored or
+// not, so it ends as the request's exact count.  Only the cursor is written on the device; the
+// initial values (cursor = 0) travel in the pass's table copy.
+struct BatchHitsWords {
+    uint64_t target;
+    unsigned long long cursor;
+    uint64_t offset;
+    uint64_t slots;
+};
+
+// One request's result of a pass, as merge_segments_hits writes it and the host copies it back.
+struct BatchHitsResult {
+    uint64_t hash, nonce, count;
+};
+
 }  // namespace mh

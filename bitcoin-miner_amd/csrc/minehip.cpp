@@ -62,6 +62,13 @@ hipError_t launch_batch_scan_first(const BatchEntry* entries, const uint32_t* ti
 hipError_t launch_merge_segments_first(const Partial* partials, const uint32_t* seg, const BatchEntry* entries,
                                        const uint32_t* tile_entry, const BatchFirstWords* words,
                                        BatchFirstResult* results, uint32_t requests, hipStream_t s);
+hipError_t launch_batch_scan_hits(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
+                                  BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
+                                  hipStream_t s);
+hipError_t launch_merge_segments_hits(const Partial* partials, const uint32_t* seg, const BatchHitsWords* words,
+                                      const Hit* hits, Hit* packed, uint64_t limit, const unsigned long long* base_in,
+                                      unsigned long long* base_out, BatchHitsResult* results, uint32_t requests,
+                                      hipStream_t s);
 }  // namespace mh
 
 namespace {
@@ -142,6 +149,11 @@ struct DevCtx {
     uint64_t* d_hcursor = nullptr;  // hits of the scan in flight
     uint64_t* h_hcursor = nullptr;  // pinned
     const mh::HitsArgs* hits = nullptr;  // set while an mh_search_hits enqueues its pieces
+    // batched hits (mh_search_hits_batch), allocated by the first such call; the hit buffer is d_hits
+    mh::BatchHitsResult* d_hres = nullptr;  // one result per request of the passes in flight
+    mh::BatchHitsResult* h_hres = nullptr;  // pinned
+    mh::Hit* d_hpacked = nullptr;   // MH_HITS_MAX_CAP entries: what the regions of a window kept, packed by the merges
+    uint64_t* d_hbase = nullptr;    // two words: entries packed by the window's passes so far (written and read in turn)
 #ifdef MH_DEV_HOOKS
     uint32_t keep = 0;        // this call's coarse-hash word (MINEHIP_DEV_HASH_KEEP; 0: unset)
     bool keep_fast = false;   // ... and the fast code object in use is the variant that reads it
@@ -1038,6 +1050,192 @@ int first_batch_run_fused(int dev, const mh::BatchRequest* reqs, const mh_first_
     return rc;
 }
 
+// ---- batched hits ----
+
+// The per-request checks of mh_search_hits_batch: batch_requests' and the cap.
+void hits_batch_requests(const mh_hits_request* reqs, size_t n, std::vector<int>* status,
+                         std::vector<mh::BatchRequest>* valid, std::vector<uint64_t>* caps) {
+    status->assign(n, MH_OK);
+    valid->clear();
+    caps->clear();
+    for (size_t i = 0; i < n; ++i) {
+        int st = check_common(reqs[i].msg, reqs[i].len);
+        if (!st && reqs[i].cap > MH_HITS_MAX_CAP) st = fail(MH_EINVAL, "cap is larger than MH_HITS_MAX_CAP");
+        if (!st && reqs[i].lower > reqs[i].upper) st = fail(MH_ERANGE, "lower > upper");
+        (*status)[i] = st;
+        if (st) continue;
+        valid->emplace_back();
+        mh::BatchRequest& r = valid->back();
+        mh::absorb_prefix(reqs[i].msg, reqs[i].len, &r.pre);
+        r.lower = reqs[i].lower;
+        r.upper = reqs[i].upper;
+        r.id = i;
+        caps->push_back(reqs[i].cap);
+    }
+}
+
+mh::HitsBatchLimits hits_batch_limits() { return mh::HitsBatchLimits{kBatchTableBytes, kBatchResults, hits_slots()}; }
+
+int hits_batch_init_locked(DevCtx* c) {
+    if (!c->d_hits) MH_HIP(hipMalloc(&c->d_hits, sizeof(mh::Hit) * MH_HITS_MAX_CAP));
+    if (!c->d_hres) MH_HIP(hipMalloc(&c->d_hres, sizeof(mh::BatchHitsResult) * kBatchResults));
+    if (!c->h_hres)
+        MH_HIP(hipHostMalloc(&c->h_hres, sizeof(mh::BatchHitsResult) * kBatchResults, hipHostMallocDefault));
+    if (!c->d_hpacked) MH_HIP(hipMalloc(&c->d_hpacked, sizeof(mh::Hit) * MH_HITS_MAX_CAP));
+    if (!c->d_hbase) MH_HIP(hipMalloc(&c->d_hbase, 2 * sizeof(uint64_t)));
+    return MH_OK;
+}
+
+// The requests of the passes enqueued since the last drain (one window), in h_hres order.
+struct HitsBatchPending {
+    std::vector<size_t> req_idx;
+    std::vector<mh::HitsRegion> region;
+    mh::HitsBatchState st;
+    uint32_t passes = 0;  // of this window
+};
+
+// The end of a window: one synchronise, one copy of the entries the window's regions kept (the
+// merges packed them, in request order: min(count, slots) per request), then per request its
+// minimum and count, and -- where its region held every hit -- its entries sorted by nonce into
+// the caller's buffer.  A request that wanted entries and has more hits than its region had slots
+// goes to *rebuild.  pend->st is left to the caller.
+int hits_batch_drain(DevCtx* c, const mh::BatchRequest* reqs, const mh_hits_request* src, HitsBatchPending* pend,
+                     mh_hit* hits, mh_hits_result* out, std::vector<size_t>* rebuild, std::vector<mh::Hit>* stage) {
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        const int rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    uint64_t kept = 0;
+    for (size_t k = 0; k < pend->req_idx.size(); ++k) kept += std::min(c->h_hres[k].count, pend->region[k].slots);
+    if (kept > pend->st.used || kept > MH_HITS_MAX_CAP) return fail(MH_EINTERNAL, "internal: hit window larger than the buffer");
+    if (stage->size() < kept) stage->resize((size_t)kept);
+    if (kept) MH_HIP(hipMemcpy(stage->data(), c->d_hpacked, (size_t)kept * sizeof(mh::Hit), hipMemcpyDeviceToHost));
+    uint64_t pos = 0;  // of the request's entries in the packed order
+    for (size_t k = 0; k < pend->req_idx.size(); ++k) {
+        const size_t id = reqs[pend->req_idx[k]].id;
+        const mh::HitsRegion& g = pend->region[k];
+        const mh::BatchHitsResult& res = c->h_hres[k];
+        mh_hits_result& r = out[id];
+        r.hash = res.hash;
+        r.nonce = res.nonce;
+        r.count = res.count;
+        r.stored = std::min<uint64_t>(res.count, src[id].cap);
+        mh::Hit* first = stage->data() + pos;
+        pos += std::min(res.count, g.slots);
+        if (!src[id].cap) continue;
+        if (res.count > g.slots) {  // the region dropped entries; which ones depends on timing
+            rebuild->push_back(pend->req_idx[k]);
+            continue;
+        }
+        // count <= slots <= cap: all of them, stored == count
+        std::sort(first, first + res.count, [](const mh::Hit& x, const mh::Hit& y) { return x.nonce < y.nonce; });
+        for (uint64_t i = 0; i < res.count; ++i) hits[r.offset + i] = mh_hit{first[i].hash, first[i].nonce};
+    }
+    pend->req_idx.clear();
+    pend->region.clear();
+    pend->passes = 0;
+    return MH_OK;
+}
+
+// batch_run_pass over the hits kernels: the pass's one H2D copy also carries the per-entry request
+// index and the requests' device words with their initial values (target; cursor = 0; the region),
+// so there is no memset and no fill kernel; then batch_scan_hits, merge_segments_hits and one D2H
+// copy of {hash, nonce, count} per request.  The passes of one window queue without a synchronise.
+int hits_batch_run_pass(DevCtx* c, const mh::BatchRequest* reqs, const mh_hits_request* src, const uint64_t* caps,
+                        const mh::BatchTables& t, uint32_t slot_cap, const mh::HitsBatchLimits& lim,
+                        HitsBatchPending* pend, mh_hit* hits, mh_hits_result* out, std::vector<size_t>* rebuild,
+                        std::vector<mh::Hit>* stage) {
+    if (!mh::batch_tables_ok(t, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t o_seg = align16(ne * sizeof(mh::BatchEntry)), o_tile = o_seg + align16((nreq + 1u) * sizeof(uint32_t));
+    const size_t o_ereq = o_tile + align16(tiles * sizeof(uint32_t)), o_words = o_ereq + align16(ne * sizeof(uint32_t));
+    const size_t bytes = o_words + align16(nreq * sizeof(mh::BatchHitsWords));
+    if (bytes != mh::hits_batch_table_bytes(ne, nreq, tiles) || bytes > kBatchTableBytes || nreq > kBatchResults)
+        return fail(MH_EINTERNAL, "internal: batch pass too large");
+    if (c->prof && c->used == kEventPairs && !pend->req_idx.empty()) {  // the event pool is full: a drain of its own
+        const int rc = hits_batch_drain(c, reqs, src, pend, hits, out, rebuild, stage);
+        if (rc) return rc;
+        mh::hits_batch_drained(&pend->st);
+    }
+    mh::HitsBatchTables ht;
+    mh::HitsBatchState next = pend->st;
+    const bool drain = mh::plan_hits_batch_pass(t, reqs, caps, lim, &next, &ht);
+    if (drain) {
+        const int rc = hits_batch_drain(c, reqs, src, pend, hits, out, rebuild, stage);
+        if (rc) return rc;
+    }
+    const uint64_t used_before = drain ? 0u : pend->st.used;
+    const size_t toff = drain ? 0u : pend->st.toff;
+    pend->st = next;
+    if (!mh::hits_batch_tables_ok(t, reqs, ht, used_before, std::min<uint64_t>(lim.window_slots, MH_HITS_MAX_CAP)) ||
+        toff + bytes > kBatchTableBytes || pend->req_idx.size() + nreq > kBatchResults)
+        return fail(MH_EINTERNAL, "internal: bad hits batch tables");
+    uint8_t* h = c->h_btab + toff;
+    uint8_t* d = c->d_btab + toff;
+    memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+    memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    memcpy(h + o_ereq, ht.entry_req.data(), ne * sizeof(uint32_t));
+    mh::BatchHitsWords* hw = (mh::BatchHitsWords*)(h + o_words);
+    for (size_t r = 0; r < nreq; ++r)
+        hw[r] = mh::BatchHitsWords{src[reqs[t.req_idx[r]].id].target, 0ull, ht.region[r].offset, ht.region[r].slots};
+    MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    Timed* tm = nullptr;
+    if (c->prof) {  // generic class, with the planned nonces, as the batch launches
+        tm = &c->pool[(size_t)c->used++];
+        tm->kind = 1;
+        tm->var = 0;
+        MH_HIP(hipEventRecord(tm->start, c->stream));
+    }
+    MH_HIP(mh::launch_batch_scan_hits((const mh::BatchEntry*)d, (const uint32_t*)(d + o_tile),
+                                      (const uint32_t*)(d + o_ereq), (mh::BatchHitsWords*)(d + o_words), c->d_hits,
+                                      c->d_partials, (uint32_t)tiles, c->stream));
+    if (tm) {
+        MH_HIP(hipEventRecord(tm->stop, c->stream));
+        c->cnt[4] += t.nonces;
+    }
+    const size_t roff = pend->req_idx.size();
+    const unsigned long long* base_in = pend->passes ? (const unsigned long long*)c->d_hbase + (pend->passes & 1u) : nullptr;
+    unsigned long long* base_out = (unsigned long long*)c->d_hbase + ((pend->passes + 1u) & 1u);
+    MH_HIP(mh::launch_merge_segments_hits(c->d_partials, (const uint32_t*)(d + o_seg),
+                                          (const mh::BatchHitsWords*)(d + o_words), c->d_hits, c->d_hpacked,
+                                          pend->st.used, base_in, base_out, c->d_hres + roff, (uint32_t)nreq, c->stream));
+    ++pend->passes;
+    MH_HIP(hipMemcpyAsync(c->h_hres + roff, c->d_hres + roff, nreq * sizeof(mh::BatchHitsResult), hipMemcpyDeviceToHost,
+                          c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    pend->region.insert(pend->region.end(), ht.region.begin(), ht.region.end());
+    return MH_OK;
+}
+
+// The fused passes of a hits batch, under the device's lock.
+int hits_batch_run_fused(int dev, const mh::BatchRequest* reqs, const mh_hits_request* src, const uint64_t* caps,
+                         const std::vector<mh::BatchItem>& items, int passes, uint32_t slot_cap, mh_hit* hits,
+                         mh_hits_result* out, std::vector<size_t>* rebuild) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (!rc) rc = hits_batch_init_locked(c);
+    if (rc) return rc;
+    const mh::HitsBatchLimits lim = hits_batch_limits();
+    HitsBatchPending pend;
+    std::vector<mh::Hit> stage;
+    mh::BatchTables t;
+    for (int p = 0; p < passes && !rc; ++p) {
+        mh::build_batch_tables(reqs, items, p, &t);
+        rc = hits_batch_run_pass(c, reqs, src, caps, t, slot_cap, lim, &pend, hits, out, rebuild, &stage);
+    }
+    if (!rc) rc = hits_batch_drain(c, reqs, src, &pend, hits, out, rebuild, &stage);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1264,6 +1462,116 @@ int64_t mh_first_batch_order(const mh_request* reqs, size_t n, int32_t pass, uin
     for (const uint32_t s : ft.order) {
         if (k >= cap) return cap + 1;  // cap + 1 signals truncation
         if (out) out[k] = s;
+        ++k;
+    }
+    return k;
+}
+
+int mh_search_hits_batch(int dev, const mh_hits_request* reqs, size_t n, mh_hit* hits, size_t hits_cap,
+                         mh_hits_result* out) {
+    g_err.clear();
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+#ifdef MH_DEV_HOOKS
+    // as mh_search_hits: the hits kernels have no variants of these hooks
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_hits_batch does not support ") + hook);
+#endif
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    std::vector<uint64_t> caps;
+    hits_batch_requests(reqs, n, &status, &valid, &caps);
+    uint64_t total = 0;  // the offsets: prefix sums of the caps, whatever the status; an out-of-range cap counts as 0
+    for (size_t i = 0; i < n; ++i) {
+        out[i] = mh_hits_result{status[i], 0, 0, 0, 0, 0, total};
+        if (reqs[i].cap <= MH_HITS_MAX_CAP) total += reqs[i].cap;
+        if (total > hits_cap) return fail(MH_EINVAL, "the caps add up to more than hits_cap");
+    }
+    if (!hits && total > 0) return fail(MH_EINVAL, "hits is NULL with a cap > 0");
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchItem> items;
+    mh::plan_batch(valid.data(), valid.size(), plan_opts(), slot_cap, &items);
+    int passes = 0;
+    for (const mh::BatchItem& it : items)
+        if (it.kind == 0) passes = std::max(passes, it.pass + 1);
+    std::vector<size_t> rebuild;  // fused requests whose region dropped entries
+    if (passes) {
+        const int rc = hits_batch_run_fused(dev, valid.data(), reqs, caps.data(), items, passes, slot_cap, hits, out,
+                                            &rebuild);
+        if (rc) return rc;
+    }
+    for (const size_t idx : rebuild) {  // the list again through the mh_search_hits path: count and minimum must agree
+        const mh::BatchRequest& r = valid[idx];
+        mh_hits_result& o = out[r.id];
+        mh_hits h;
+        const int rc = search_hits_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, hits + o.offset,
+                                        (size_t)reqs[r.id].cap, &h);
+        if (rc) return rc;
+        if (h.count != o.count || h.hash != o.hash || h.nonce != o.nonce || h.stored != o.stored)
+            return fail(MH_EINTERNAL, "internal: a rebuilt hit list disagrees with the fused scan");
+    }
+    for (const mh::BatchItem& it : items) {  // the fallbacks, after the fused passes
+        if (it.kind != 1) continue;
+        const mh::BatchRequest& r = valid[it.idx];
+        mh_hits_result& o = out[r.id];
+        mh_hits h;
+        const int rc = search_hits_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target,
+                                        reqs[r.id].cap ? hits + o.offset : nullptr, (size_t)reqs[r.id].cap, &h);
+        if (rc) return rc;
+        o.count = h.count;
+        o.stored = h.stored;
+        o.hash = h.hash;
+        o.nonce = h.nonce;
+    }
+    return MH_OK;
+}
+
+int64_t mh_hits_batch_regions(const mh_hits_request* reqs, size_t n, mh_hits_region* out, int64_t cap) {
+    g_err.clear();
+    if (n == 0) return 0;
+    if (!reqs) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> all;
+    std::vector<uint64_t> caps;
+    hits_batch_requests(reqs, n, &status, &all, &caps);
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])  // the first request mh_search_hits_batch would refuse
+            return fail(status[i], status[i] == MH_ERANGE     ? "lower > upper"
+                                   : status[i] == MH_ETOOLONG ? "message longer than MH_MAX_MSG_LEN"
+                                   : reqs[i].cap > MH_HITS_MAX_CAP ? "cap is larger than MH_HITS_MAX_CAP"
+                                                                   : "msg is NULL");
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchItem> items;
+    mh::plan_batch(all.data(), n, plan_opts(), slot_cap, &items);
+    int passes = 0;
+    for (const mh::BatchItem& it : items)
+        if (it.kind == 0) passes = std::max(passes, it.pass + 1);
+    std::vector<mh_hits_region> regions(n);
+    for (const mh::BatchItem& it : items)
+        if (it.kind == 1) regions[it.idx] = mh_hits_region{it.req, 1, -1, -1, 0, 0, 0};
+    const mh::HitsBatchLimits lim = hits_batch_limits();
+    mh::HitsBatchState st;
+    mh::BatchTables t;
+    mh::HitsBatchTables ht;
+    for (int p = 0; p < passes; ++p) {
+        mh::build_batch_tables(all.data(), items, p, &t);
+        if (!mh::batch_tables_ok(t, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+        const uint64_t before = st.used;
+        const bool drain = mh::plan_hits_batch_pass(t, all.data(), caps.data(), lim, &st, &ht);
+        if (!mh::hits_batch_tables_ok(t, all.data(), ht, drain ? 0u : before, lim.window_slots))
+            return fail(MH_EINTERNAL, "internal: bad hits batch tables");
+        for (size_t r = 0; r < t.req_idx.size(); ++r)
+            regions[t.req_idx[r]] = mh_hits_region{all[t.req_idx[r]].id, 0, p, st.window, 0, ht.region[r].offset,
+                                                   ht.region[r].slots};
+    }
+    int64_t k = 0;
+    for (const mh_hits_region& g : regions) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = g;
         ++k;
     }
     return k;

@@ -653,14 +653,32 @@ bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap) {
 
 // ---- batched first-hit search ----
 
-void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchTables* out) {
-    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
-    out->entry_req.assign(t.entries.size(), 0u);
+namespace {
+// Per entry of a pass its request (index into seg / req_idx), for the kernels whose tiles find
+// per-request device words; and the check that every entry's request owns the entry's slots.
+void entry_requests(const BatchTables& t, std::vector<uint32_t>* entry_req) {
+    const size_t nreq = t.req_idx.size();
+    entry_req->assign(t.entries.size(), 0u);
     size_t r = 0;
     for (size_t ei = 0; ei < t.entries.size(); ++ei) {  // entries and segments are both in slot order
         while (r + 1 < nreq && t.seg[r + 1] <= t.entries[ei].slot0) ++r;
-        out->entry_req[ei] = (uint32_t)r;
+        (*entry_req)[ei] = (uint32_t)r;
     }
+}
+bool entry_requests_ok(const BatchTables& t, const std::vector<uint32_t>& entry_req) {
+    const size_t nreq = t.req_idx.size();
+    if (entry_req.size() != t.entries.size() || t.seg.size() != nreq + 1u) return false;
+    for (size_t ei = 0; ei < t.entries.size(); ++ei) {
+        const uint32_t r = entry_req[ei];
+        if (r >= nreq || t.entries[ei].slot0 < t.seg[r] || t.entries[ei].slot0 >= t.seg[r + 1]) return false;
+    }
+    return true;
+}
+}  // namespace
+
+void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchTables* out) {
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    entry_requests(t, &out->entry_req);
     out->order.clear();
     out->order.reserve(tiles);
     if (!rank_major) {
@@ -683,18 +701,75 @@ void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchT
 }
 
 bool first_batch_tables_ok(const BatchTables& t, const FirstBatchTables& f) {
-    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
-    if (f.entry_req.size() != t.entries.size() || f.order.size() != tiles || t.seg.size() != nreq + 1u) return false;
-    for (size_t ei = 0; ei < t.entries.size(); ++ei) {
-        const uint32_t r = f.entry_req[ei];
-        if (r >= nreq || t.entries[ei].slot0 < t.seg[r] || t.entries[ei].slot0 >= t.seg[r + 1]) return false;
-    }
+    const size_t tiles = t.tile_entry.size();
+    if (!entry_requests_ok(t, f.entry_req) || f.order.size() != tiles) return false;
     std::vector<bool> seen(tiles, false);
     for (const uint32_t s : f.order) {
         if (s >= tiles || seen[s]) return false;
         seen[s] = true;
     }
     return true;  // tiles distinct values below tiles: a permutation
+}
+
+// ---- batched hits ----
+
+namespace {
+inline size_t align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+// nonces of a request, saturating (a fused request is far smaller)
+inline uint64_t request_size(const BatchRequest& r) {
+    const uint64_t d = r.upper - r.lower;
+    return d == ~(uint64_t)0 ? d : d + 1u;
+}
+}  // namespace
+
+size_t hits_batch_table_bytes(size_t entries, size_t requests, size_t tiles) {
+    return align16(entries * sizeof(BatchEntry)) + align16((requests + 1u) * sizeof(uint32_t)) +
+           align16(tiles * sizeof(uint32_t)) + align16(entries * sizeof(uint32_t)) +
+           align16(requests * sizeof(BatchHitsWords));
+}
+
+void hits_batch_drained(HitsBatchState* st) {
+    st->toff = st->nres = 0;
+    st->used = 0;
+    ++st->window;
+}
+
+bool plan_hits_batch_pass(const BatchTables& t, const BatchRequest* reqs, const uint64_t* caps,
+                          const HitsBatchLimits& lim, HitsBatchState* st, HitsBatchTables* out) {
+    const size_t nreq = t.req_idx.size();
+    const size_t bytes = hits_batch_table_bytes(t.entries.size(), nreq, t.tile_entry.size());
+    uint64_t want = 0;  // <= kBatchMaxRequests * MH_HITS_MAX_CAP-sized caps: no overflow
+    for (size_t r = 0; r < nreq; ++r) want += std::min(caps[t.req_idx[r]], request_size(reqs[t.req_idx[r]]));
+    const bool in_flight = st->toff != 0 || st->nres != 0 || st->used != 0;
+    const bool drain = in_flight && (st->toff + bytes > lim.table_bytes || st->nres + nreq > lim.results ||
+                                     (st->used != 0 && want > lim.window_slots - std::min(st->used, lim.window_slots)));
+    if (drain) hits_batch_drained(st);
+    entry_requests(t, &out->entry_req);
+    out->region.clear();
+    out->region.reserve(nreq);
+    for (size_t r = 0; r < nreq; ++r) {
+        const uint64_t left = lim.window_slots - std::min(st->used, lim.window_slots);
+        const uint64_t slots = std::min(std::min(caps[t.req_idx[r]], request_size(reqs[t.req_idx[r]])), left);
+        out->region.push_back(HitsRegion{st->used, slots});
+        st->used += slots;
+    }
+    st->toff += bytes;
+    st->nres += nreq;
+    return drain;
+}
+
+bool hits_batch_tables_ok(const BatchTables& t, const BatchRequest* reqs, const HitsBatchTables& h,
+                          uint64_t used_before, uint64_t window_slots) {
+    const size_t nreq = t.req_idx.size();
+    if (!entry_requests_ok(t, h.entry_req) || h.region.size() != nreq) return false;
+    uint64_t next = used_before;
+    for (size_t r = 0; r < nreq; ++r) {
+        const HitsRegion& g = h.region[r];
+        if (g.offset < next || g.offset > window_slots || g.slots > window_slots - g.offset) return false;
+        if (g.slots > request_size(reqs[t.req_idx[r]])) return false;
+        next = g.offset + g.slots;
+    }
+    return true;
 }
 
 }  // namespace mh

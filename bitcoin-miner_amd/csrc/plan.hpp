@@ -218,4 +218,50 @@ void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchT
 // segment holds the entry's slots, and order is a permutation of the pass's tiles.
 bool first_batch_tables_ok(const BatchTables& t, const FirstBatchTables& f);
 
+// ---- batched hits (mh_search_hits_batch / mh_hits_batch_regions) ----
+// The tables batch_scan_hits reads beside a pass's BatchTables (the plan depends neither on the
+// targets nor on the caps, so plan_batch and build_batch_tables serve unchanged), and the schedule
+// of the passes: which ones start after a drain.  The device hit buffer is handed out in windows:
+// between two drains the fused requests of the passes in flight own disjoint regions of it, in
+// request order.
+struct HitsRegion {
+    uint64_t offset, slots;  // entries offset .. offset + slots - 1 of the device hit buffer
+};
+struct HitsBatchTables {
+    std::vector<uint32_t> entry_req;  // per entry: its request of the pass (index into seg / req_idx)
+    std::vector<HitsRegion> region;   // per request of the pass
+};
+// What the passes in flight may use before a drain empties it all: bytes of the table buffer,
+// results, and entries of the device hit buffer (window_slots >= 1).
+struct HitsBatchLimits {
+    size_t table_bytes, results;
+    uint64_t window_slots;
+};
+// In use since the last drain, and how many drains there were.
+struct HitsBatchState {
+    size_t toff = 0, nres = 0;
+    uint64_t used = 0;
+    int window = 0;
+};
+// Bytes of one pass's tables in the table buffer: entries, segments, per-tile entry, per-entry
+// request, per-request words, each aligned to 16 bytes.
+size_t hits_batch_table_bytes(size_t entries, size_t requests, size_t tiles);
+// A drain: everything in flight is home, the next window starts.
+void hits_batch_drained(HitsBatchState* st);
+// Plan pass `t` behind the passes in *st: it starts after a drain (the return value; *st is then
+// hits_batch_drained first) when its tables or results do not fit behind those in flight, or when
+// its requests want more slots than the window has left and the window is not empty -- a request
+// wants min(cap, its nonce count), caps[BatchItem::idx] being its cap.  Then, in request order,
+// request r gets slots = min(cap, its nonce count, slots left in the window) at the next free
+// offset, and *st advances.  A request that got fewer slots than it has hits is rebuilt by the
+// caller (minehip.cpp).
+bool plan_hits_batch_pass(const BatchTables& t, const BatchRequest* reqs, const uint64_t* caps,
+                          const HitsBatchLimits& lim, HitsBatchState* st, HitsBatchTables* out);
+// Checked before every launch, after batch_tables_ok(t): every entry's request is the one whose
+// segment holds the entry's slots; one region per request of the pass, each no larger than its
+// request's nonce count, in order and disjoint, none below used_before (where the regions of the
+// window's earlier passes end) and none beyond window_slots.
+bool hits_batch_tables_ok(const BatchTables& t, const BatchRequest* reqs, const HitsBatchTables& h,
+                          uint64_t used_before, uint64_t window_slots);
+
 }  // namespace mh

@@ -33,6 +33,10 @@
 //                         words, tiles dispatched in the host's rank-major order.
 //   merge_segments_first  merge_segments, then the winning key back into its hash and the
 //                         request's {hash, nonce, scanned} out.
+//   batch_scan_hits       batch_scan for mh_search_hits_batch: the same minimum, and every nonce
+//                         whose hash is <= its request's target appended to the request's region
+//                         of the device hit buffer through a per-request cursor.
+//   merge_segments_hits   merge_segments, and the request's {hash, nonce, count} out.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -274,9 +278,14 @@ namespace dev {
 // FIRST: the first-hit key (batch_scan_first): a hash <= target counts as 0, so the fold keeps the
 // smallest qualifying nonce; no test hooks there (mh_search_first_batch refuses them).  Without
 // FIRST, target is unused and the function is batch_scan's as before.
-template <bool FIRST>
+// HITS (batch_scan_hits): the product's own (hash, nonce) fold, and on a rare branch every nonce
+// with hash <= target takes one slot from its request's cursor and stores {hash, nonce} at
+// region[slot] if slot < region_slots (layout.hpp BatchHitsWords); no test hooks there either
+// (mh_search_hits_batch refuses them).  Without HITS the three last parameters are unused.
+template <bool FIRST, bool HITS = false>
 __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32_t jlo, uint32_t jhi, uint64_t target,
-                                            uint64_t& bh, uint64_t& bn) {
+                                            uint64_t& bh, uint64_t& bn, unsigned long long* cursor = nullptr,
+                                            Hit* region = nullptr, uint64_t region_slots = 0) {
     // digits of u; u <= (2^64 - 1) / 10 has at most 19
     constexpr uint64_t P10[19] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
                                   100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull,
@@ -354,7 +363,7 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
         uint32_t h0, h1;
         sha256_block_h01(s, x, h0, h1);
 #ifdef MH_DEV_HOOKS  // hash-XOR and coarse-hash test hooks, as in generic_scan
-        if constexpr (!FIRST) {
+        if constexpr (!FIRST && !HITS) {
             h0 = (h0 ^ mh_dev_hash_xor[0]) & keep_mask0(a.pad);
             h1 = (h1 ^ mh_dev_hash_xor[1]) & keep_mask1(a.pad);
         }
@@ -363,6 +372,12 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
         const uint64_t n = n0 + j;
         if constexpr (FIRST) {
             if (hash <= target) hash = 0ull;
+        }
+        if constexpr (HITS) {
+            if (hash <= target) {  // rare with a sparse target
+                const unsigned long long slot = atomicAdd(cursor, 1ull);
+                if (slot < region_slots) region[slot] = Hit{hash, n};
+            }
         }
         if (lex_less(hash, n, bh, bn)) {
             bh = hash;
@@ -464,6 +479,48 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEnt
     }
 }
 
+// batch_scan for mh_search_hits_batch: batch_scan's static grid and identity tile
+// order -- workgroup b runs tile b and writes partials[b] -- with the product's (hash, nonce)
+// minimum, so slots, segments and merge keep batch_scan's layout and give mh_search's result.  The
+// tile's request (entry_req[entry]) has four device words (layout.hpp BatchHitsWords): every nonce
+// with Hash <= target takes one slot from the request's cursor and stores {hash, nonce} at entry
+// offset + slot of the device hit buffer only if slot < slots, so nothing is written outside the
+// request's region (the host checks the regions of a window before every launch: inside the
+// buffer and disjoint).  Every nonce of a request belongs to exactly one (tile, lane, digit) and
+// every tile runs exactly once, so the cursor ends as the request's exact count.  No skipping, no
+// waiting, no dependency between workgroups: the grid always drains.  No test hooks.
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_hits(const BatchEntry* __restrict__ entries,
+                                                                 const uint32_t* __restrict__ tile_entry,
+                                                                 const uint32_t* __restrict__ entry_req,
+                                                                 BatchHitsWords* words, Hit* hits,
+                                                                 Partial* __restrict__ partials) {
+    using namespace dev;
+    const uint32_t ei = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_entry[blockIdx.x]);
+    const uint32_t ri = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry_req[ei]);
+    const BatchEntry& e = entries[ei];
+    const GenArgs& a = e.g;
+    BatchHitsWords* w = words + ri;
+    const uint64_t target = w->target, region_slots = w->slots;  // never written on the device
+    Hit* region = hits + w->offset;
+    const uint64_t first = a.first, lastn = a.first + (a.count - 1u);
+    const uint64_t u_first = first / 10u, u_last = lastn / 10u;
+    const uint32_t j_first = (uint32_t)(first - u_first * 10u), j_last = (uint32_t)(lastn - u_last * 10u);
+    const uint64_t nd = u_last - u_first + 1u;
+    const uint64_t base = (uint64_t)(blockIdx.x - e.tile0) * kBatchTileDecades;
+    uint64_t bh = ~0ull, bn = ~0ull;
+#pragma unroll 1
+    for (int k = 0; k < kBatchDecades; ++k) {
+        const uint64_t off = base + (uint32_t)k * (uint32_t)kBlockThreads + threadIdx.x;
+        if (off < nd) {
+            const uint64_t u = u_first + off;
+            scan_decade<false, true>(a, u, off == 0u ? j_first : 0u, u == u_last ? j_last : 9u, target, bh, bn,
+                                     &w->cursor, region, region_slots);
+        }
+    }
+    block_min(bh, bn);
+    if (threadIdx.x == 0) partials[blockIdx.x] = Partial{bh, bn};
+}
+
 // One workgroup per request of the pass: results[r] = the lexicographic minimum of
 // partials[seg[r] .. seg[r + 1]) (never empty; the host checks the table before the launch).
 __global__ __launch_bounds__(kBlockThreads) void merge_segments(const Partial* __restrict__ partials,
@@ -516,6 +573,55 @@ __global__ __launch_bounds__(kBlockThreads) void merge_segments_first(const Part
         }
         results[r] = BatchFirstResult{h, n, words[r].scanned};
     }
+}
+
+// merge_segments for mh_search_hits_batch: the same fold, and results[r] = {hash, nonce, the
+// request's cursor}, final since every tile of the pass has run (stream order).  Then the entries
+// the request's region kept, min(cursor, slots) of them, move to packed[]: behind those of the
+// pass's earlier requests (every workgroup sums them itself: at most 4,096 words) and of the
+// window's earlier passes (*base_in, written by the last workgroup of the pass before; null in a
+// window's first pass: 0), so that a drain copies home the entries stored and not the regions'
+// whole extent.  The last workgroup writes the running total to *base_out, another word than
+// *base_in.  Nothing is stored at or beyond packed[limit], where the window's regions end.
+__global__ __launch_bounds__(kBlockThreads) void merge_segments_hits(const Partial* __restrict__ partials,
+                                                                     const uint32_t* __restrict__ seg,
+                                                                     const BatchHitsWords* __restrict__ words,
+                                                                     const Hit* __restrict__ hits,
+                                                                     Hit* __restrict__ packed, uint64_t limit,
+                                                                     const unsigned long long* base_in,
+                                                                     unsigned long long* base_out,
+                                                                     BatchHitsResult* __restrict__ results) {
+    using namespace dev;
+    __shared__ unsigned long long s_before;
+    const uint32_t r = blockIdx.x;
+    if (threadIdx.x == 0) s_before = base_in ? *base_in : 0ull;
+    __syncthreads();
+    unsigned long long before = 0ull;
+    for (uint32_t j = threadIdx.x; j < r; j += kBlockThreads) {
+        const unsigned long long c = words[j].cursor, sl = words[j].slots;
+        before += c < sl ? c : sl;
+    }
+    if (before) atomicAdd(&s_before, before);
+    __syncthreads();
+    const uint64_t base = s_before;
+    const uint64_t count = words[r].cursor;
+    const uint64_t kept = count < words[r].slots ? count : words[r].slots;
+    const Hit* region = hits + words[r].offset;
+    for (uint64_t i = threadIdx.x; i < kept; i += kBlockThreads)
+        if (base + i < limit) packed[base + i] = region[i];
+    if (threadIdx.x == 0 && r + 1u == gridDim.x) *base_out = base + kept;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r]);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r + 1]);
+    uint64_t h = ~0ull, n = ~0ull;
+    for (uint32_t i = a + threadIdx.x; i < b; i += kBlockThreads) {
+        const Partial x = partials[i];
+        if (lex_less(x.hash, x.nonce, h, n)) {
+            h = x.hash;
+            n = x.nonce;
+        }
+    }
+    block_min(h, n);
+    if (threadIdx.x == 0) results[r] = BatchHitsResult{h, n, count};
 }
 
 // ---------------------------------------------------------------------------
@@ -820,6 +926,25 @@ hipError_t launch_merge_segments_first(const Partial* partials, const uint32_t* 
                                        BatchFirstResult* results, uint32_t requests, hipStream_t s) {
     hipLaunchKernelGGL(merge_segments_first, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, entries,
                        tile_entry, words, results);
+    return hipGetLastError();
+}
+
+// One pass of a hits batch: tiles workgroups of batch_scan_hits, then requests workgroups of
+// merge_segments_hits (the caller has checked the tables and the regions, minehip.cpp hits_batch_run_pass).
+hipError_t launch_batch_scan_hits(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
+                                  BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
+                                  hipStream_t s) {
+    hipLaunchKernelGGL(batch_scan_hits, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req, words,
+                       hits, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_segments_hits(const Partial* partials, const uint32_t* seg, const BatchHitsWords* words,
+                                      const Hit* hits, Hit* packed, uint64_t limit, const unsigned long long* base_in,
+                                      unsigned long long* base_out, BatchHitsResult* results, uint32_t requests,
+                                      hipStream_t s) {
+    hipLaunchKernelGGL(merge_segments_hits, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, words, hits, packed,
+                       limit, base_in, base_out, results);
     return hipGetLastError();
 }
 

@@ -31,6 +31,7 @@ from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
 from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
 from ._lib import mh_first_request, mh_first_result  # noqa: F401
 from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP  # noqa: F401
+from ._lib import mh_hits_request, mh_hits_result, mh_hits_region  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -207,6 +208,75 @@ def first_batch_order(requests, pass_=0, cap=1 << 18):
     if k > cap:
         raise ValueError("order longer than cap")
     return list(buf[:k])
+
+
+def _hits_requests(requests, cap):
+    """(msg, lower, upper, target[, cap]) tuples -> (mh_hits_request array, the message bytes it
+    points into, the offsets of the requests' entries, their sum)."""
+    if not isinstance(cap, int) or isinstance(cap, bool) or not 0 <= cap <= U64_MAX:
+        raise ValueError(f"cap = {cap!r} is not a uint64")
+    keep, offsets, total = [], [], 0
+    arr = (mh_hits_request * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        try:
+            msg, lower, upper, target, c = r if len(r) == 5 else tuple(r) + (cap,)
+        except (TypeError, ValueError):
+            raise ValueError(f"request {i}: expected (msg, lower, upper, target[, cap]), got {r!r}") from None
+        for name, v in (("lower", lower), ("upper", upper), ("target", target), ("cap", c)):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U64_MAX:
+                raise ValueError(f"request {i}: {name} = {v!r} is not a uint64")
+        m = _b(msg)
+        keep.append(m)
+        arr[i].msg, arr[i].len, arr[i].lower, arr[i].upper, arr[i].target, arr[i].cap = m, len(m), lower, upper, target, c
+        offsets.append(total)
+        total += c if c <= MH_HITS_MAX_CAP else 0       # as the library counts them
+    return arr, keep, offsets, total
+
+
+def search_hits_batch(requests, cap=4096, dev=0, errors="raise"):
+    """[(count, [(nonce, hash), ...], (min_hash, min_nonce)), ...] of many (msg, lower, upper,
+    target) or (msg, lower, upper, target, cap) requests, each exactly what search_hits() gives,
+    with the small ones fused into one GPU pass (mh_search_hits_batch); `cap` is the cap of the
+    requests that carry none.  Per-request failures as search_batch: raised with the request's
+    index, or with errors="return" left in place in the list."""
+    if errors not in ("raise", "return"):
+        raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
+    requests = list(requests)
+    arr, keep, offsets, total = _hits_requests(requests, cap)
+    # not a ctypes array: that would be zero-filled, all sum-of-caps entries of it, on every call
+    buf = np.empty((max(1, total), 2), dtype=np.uint64)
+    out = (mh_hits_result * max(1, len(requests)))()
+    _check(lib.mh_search_hits_batch(dev, arr, len(requests), buf.ctypes.data_as(ctypes.POINTER(mh_hit)) if total else None,
+                                    total, out))
+    res = []
+    for i in range(len(requests)):
+        o = out[i]
+        if o.status == MH_OK:
+            assert o.offset == offsets[i]
+            entries = [(n, h) for h, n in buf[o.offset:o.offset + o.stored].tolist()] if o.stored else []
+            res.append((o.count, entries, (o.hash, o.nonce)))
+            continue
+        what = ("cap is larger than MH_HITS_MAX_CAP" if o.status == MH_EINVAL and arr[i].cap > MH_HITS_MAX_CAP
+                else _REQUEST_ERRORS.get(o.status, "failed"))
+        e = MinehipError(o.status, f"request {i}: {what}")
+        e.index = i
+        if errors == "raise":
+            raise e
+        res.append(e)
+    return res
+
+
+def hits_batch_regions(requests, cap=4096):
+    """Host-only: how search_hits_batch would run the requests -- one dict per request: kind (0
+    fused, 1 fallback), its pass, its window (how many drains precede it) and its region (offset,
+    slots) of the device hit buffer (mh_hits_batch_regions)."""
+    requests = list(requests)
+    arr, keep, _, _ = _hits_requests(requests, cap)
+    buf = (mh_hits_region * max(1, len(requests)))()
+    k = lib.mh_hits_batch_regions(arr, len(requests), buf, len(requests))
+    if k < 0:
+        _check(k)
+    return [{f: getattr(buf[i], f) for f, _ in mh_hits_region._fields_ if f != "reserved"} for i in range(k)]
 
 
 def hash_batch(msg, nonces, dev=0):

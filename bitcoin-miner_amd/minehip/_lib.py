@@ -36,6 +36,7 @@ EXPORTS = (
     "mh_profile_enable", "mh_profile_read", "mh_profile_kernels", "mh_plan", "mh_multi_plan",
     "mh_multi_rates", "mh_search_batch", "mh_batch_plan", "mh_miner_handle_batch",
     "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
+    "mh_search_hits_batch", "mh_hits_batch_regions",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -95,6 +96,23 @@ class mh_first_request(ctypes.Structure):
 class mh_first_result(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("found", ctypes.c_int32), ("hash", ctypes.c_uint64),
                 ("nonce", ctypes.c_uint64), ("scanned", ctypes.c_uint64)]
+
+
+class mh_hits_request(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t), ("lower", ctypes.c_uint64),
+                ("upper", ctypes.c_uint64), ("target", ctypes.c_uint64), ("cap", ctypes.c_uint64)]
+
+
+class mh_hits_result(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("count", ctypes.c_uint64),
+                ("stored", ctypes.c_uint64), ("hash", ctypes.c_uint64), ("nonce", ctypes.c_uint64),
+                ("offset", ctypes.c_uint64)]
+
+
+class mh_hits_region(ctypes.Structure):
+    _fields_ = [("req", ctypes.c_uint64), ("kind", ctypes.c_int32), ("pass", ctypes.c_int32),
+                ("window", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64),
+                ("slots", ctypes.c_uint64)]
 
 
 class mh_batch_item(ctypes.Structure):
@@ -172,6 +190,10 @@ def _load():
                                         ctypes.POINTER(mh_first_result)]
     L.mh_first_batch_order.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.c_int32,
                                        ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64]
+    L.mh_search_hits_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hit), sz,
+                                       ctypes.POINTER(mh_hits_result)]
+    L.mh_hits_batch_regions.argtypes = [ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hits_region),
+                                        ctypes.c_int64]
     L.mh_batch_plan.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_batch_item), ctypes.c_int64]
     L.mh_miner_handle_batch.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz,
                                         ctypes.c_char_p, sz, ctypes.POINTER(sz), intp]
@@ -195,7 +217,8 @@ def _load():
     L.mh_server_pop_write.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_char_p, sz, ctypes.POINTER(sz)]
     L.mh_server_stats.argtypes = [vp, ctypes.POINTER(mh_sched_stats)]
     restype = {"mh_plan": ctypes.c_int64, "mh_multi_plan": ctypes.c_int64, "mh_batch_plan": ctypes.c_int64,
-               "mh_first_batch_order": ctypes.c_int64, "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
+               "mh_first_batch_order": ctypes.c_int64, "mh_hits_batch_regions": ctypes.c_int64,
+               "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
                "mh_sched_destroy": None, "mh_server_destroy": None}
     for name in EXPORTS:

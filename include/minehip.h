@@ -218,10 +218,60 @@ typedef struct mh_hits {
  * `stored` entries are collected.  Nothing returned depends on the launch plan, the streams, the
  * queue mode, the timing or the size of that buffer.
  * Errors: MH_EINVAL for out == NULL, cap > MH_HITS_MAX_CAP, or hits == NULL with cap > 0;
- * MH_ERANGE, MH_ETOOLONG, MH_ENODEV as mh_search.  One device only; no batched form, nothing in
- * the LSP protocol.  Additive in ABI 5 (no existing struct changes). */
+ * MH_ERANGE, MH_ETOOLONG, MH_ENODEV as mh_search.  One device only; nothing in the LSP protocol;
+ * the batched form is mh_search_hits_batch below.  Additive in ABI 5 (no existing struct changes). */
 int mh_search_hits(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                    uint64_t target, mh_hit *hits, size_t cap, mh_hits *out);
+
+/* ---- batched hits: every hit of many small Requests in one pass ----------- */
+
+typedef struct mh_hits_request {
+    const uint8_t *msg;
+    size_t len;
+    uint64_t lower, upper, target;
+    uint64_t cap; /* most entries wanted for this request, <= MH_HITS_MAX_CAP; 0: count only */
+} mh_hits_request; /* 48 bytes */
+
+typedef struct mh_hits_result {
+    int32_t status, reserved; /* MH_OK, or the MH_E* of this request alone */
+    uint64_t count, stored;   /* as mh_hits: exact count; stored = min(count, cap) */
+    uint64_t hash, nonce;     /* exactly what mh_search returns for the range */
+    uint64_t offset;          /* this request's entries are hits[offset .. offset + stored) */
+} mh_hits_result; /* 48 bytes */
+
+/* For every request whose status is MH_OK: count, stored, hash, nonce and the `stored` entries at
+ * hits + offset are exactly what mh_search_hits(dev, msg, len, lower, upper, target, hits + offset,
+ * cap, ...) gives -- the min(count, cap) smallest qualifying nonces in strictly increasing nonce
+ * order, each with its hash, and the range's minimum whether or not anything qualifies.  Nothing
+ * returned depends on pass packing, the fused / fallback split, the size of the device hit buffer
+ * or timing.
+ * offset of request i is the sum of cap over requests 0 .. i-1 whatever their status, a cap above
+ * MH_HITS_MAX_CAP counting as 0: the caller can compute the offsets beforehand, and the regions
+ * never overlap.  hits holds hits_cap entries.
+ * Fused or fallback is decided as in mh_search_batch (the plan depends neither on the targets nor
+ * on the caps: mh_batch_plan shows it).  The fused requests run as 2,560-nonce tiles of one launch
+ * of the batch_scan_hits kernel per pass -- batch_scan with an append of every hit through a
+ * per-request cursor into the request's region of the device hit buffer -- one segmented merge and
+ * one copy-back of {hash, nonce, count} per pass; the whole range is hashed, there is no early
+ * end, since the count needs it.  The device hit buffer holds MH_HITS_MAX_CAP entries
+ * (MINEHIP_HITS_SLOTS, read per call, lowers that for tests) and is handed out in windows: a
+ * request gets min(cap, its nonce count, what the window has left) entries, and a pass whose
+ * requests want more than the window has left starts a new window after a drain (one host
+ * synchronise and one copy of the entries stored; mh_hits_batch_regions shows the schedule).  A
+ * batch whose wants fit one window has one synchronise.  A fallback request runs through the
+ * mh_search_hits path after the fused passes.
+ * Asking for fewer entries than qualify (0 < cap < count, or a region cut short by the window)
+ * costs that request a second scan: which entries its region kept depends on timing, so its list
+ * is rebuilt through the mh_search_hits path; cap == 0 never needs that.  Built for sparse
+ * targets, as mh_search_hits: a loose one is correct but slow.
+ * Per-request failures go to out[i].status and do not stop the others: MH_ERANGE, MH_ETOOLONG,
+ * MH_EINVAL (msg NULL with len > 0, or cap > MH_HITS_MAX_CAP).  For the call: MH_EINVAL for NULL
+ * reqs or out with n > 0, for the sum of the caps (as counted for offset) above hits_cap, and for
+ * hits == NULL with that sum above 0; n == 0 returns MH_OK without touching a device; a
+ * device-level failure (MH_ENODEV, MH_EHIP, MH_EINTERNAL) is the call's return code and leaves
+ * out undefined.  One device only; nothing in the LSP protocol or the miner.  Additive in ABI 5. */
+int mh_search_hits_batch(int dev, const mh_hits_request *reqs, size_t n, mh_hit *hits, size_t hits_cap,
+                         mh_hits_result *out);
 
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
@@ -361,6 +411,21 @@ int64_t mh_batch_plan(const mh_request *reqs, size_t n, mh_batch_item *out, int6
  * cap + 1 when there are more than cap (the first cap written, as mh_plan), the MH_E* of the
  * first request mh_search would refuse, or MH_EINVAL when the plan has no such pass. */
 int64_t mh_first_batch_order(const mh_request *reqs, size_t n, int32_t pass, uint32_t *out, int64_t cap);
+
+/* One request of mh_search_hits_batch's schedule. */
+typedef struct mh_hits_region {
+    uint64_t req;          /* index into reqs */
+    int32_t kind, pass;    /* 0 fused, 1 fallback; its pass, exactly mh_batch_plan's (fallback: -1) */
+    int32_t window, reserved; /* fused: how many drains precede its pass; fallback: -1 */
+    uint64_t offset, slots;   /* fused: its region of the device hit buffer; fallback: 0, 0 */
+} mh_hits_region; /* 40 bytes */
+
+/* Host only: how mh_search_hits_batch would run reqs[0..n): one item per request, in request
+ * order.  The regions of one window are disjoint, in order and inside the device hit buffer
+ * (honours MINEHIP_HITS_SLOTS and MINEHIP_BATCH_SLOTS).  Returns the item count, cap + 1 when
+ * there are more than cap (the first cap written, as mh_plan), or the MH_E* of the first request
+ * mh_search_hits_batch would refuse.  n == 0 returns 0. */
+int64_t mh_hits_batch_regions(const mh_hits_request *reqs, size_t n, mh_hits_region *out, int64_t cap);
 
 /* One span of mh_search_multi's adaptive split (chunk == 0), ABI 4. */
 typedef struct mh_span {
