@@ -25,12 +25,18 @@ FASTFLAGS ?=
 # (embedded in the library), the coarse-hash test variant (-DMH_HASH_KEEP) and the
 # first-hit kernels first_scan<J, MODE> of mh_search_first (-DMH_FIRST; embedded too)
 # and the hits kernels hits_scan<J, MODE> of mh_search_hits (-DMH_HITS; embedded too)
-FAST_NAMES := fast_search fast_search_keep fast_first fast_hits
+# and the batch kernels batch_fast<J, MODE> of mh_search_batch_ex (-DMH_BATCH; embedded
+# too) with their coarse-hash test variant (-DMH_BATCH -DMH_HASH_KEEP, the dev build's
+# MINEHIP_DEV_BATCH_CODE_OBJECT)
+FAST_NAMES := fast_search fast_search_keep fast_first fast_hits fast_batch fast_batch_keep
 FASTFLAGS_fast_search_keep := -DMH_HASH_KEEP
 FASTFLAGS_fast_first := -DMH_FIRST
 FASTFLAGS_fast_hits := -DMH_HITS
+FASTFLAGS_fast_batch := -DMH_BATCH
+FASTFLAGS_fast_batch_keep := -DMH_BATCH -DMH_HASH_KEEP
 FIRST_CO := $(BUILD)/fast_first.hsaco
 HITS_CO := $(BUILD)/fast_hits.hsaco
+BATCH_CO := $(BUILD)/fast_batch.hsaco
 
 LSPLIB  := $(PKG)/minehip/liblsp440.so
 APPS    := $(CSRC)/apps
@@ -41,7 +47,7 @@ RPATH   := -Wl,-rpath,'$$ORIGIN/../minehip'
 DEVLIB  := $(BUILD)/dev/libminehip.so
 
 all: $(LIB) $(LSPLIB) $(CLIS) oracle dev $(BUILD)/libclockprobe.so $(BUILD)/libvaluenergy.so $(FAST_MIX) $(BUILD)/fast_search_nomarker.hsaco \
-     $(BUILD)/fast_search_keep.hsaco
+     $(BUILD)/fast_search_keep.hsaco $(BUILD)/fast_batch_keep.hsaco
 
 # LSP endpoint (host only, wire compatible with the reference's Go lsp package)
 $(LSPLIB): $(CSRC)/lsp/lsp.cpp include/lsp440.h
@@ -77,10 +83,12 @@ $(ADD3_STAMP):
 	touch $@
 $(FAST_NAMES:%=$(BUILD)/%_split.s): $(BUILD)/%_split.s: $(BUILD)/%.s $(CSRC)/add3_split.py $(ADD3_STAMP)
 	python3 $(CSRC)/add3_split.py $(ADD3_SPLIT) $< $@ $(ADD3_LIKE_$*)
-# the first-hit and hits builds split their per-nonce loops as the product's are split (add3_split.py, like_split.s)
+# the first-hit, hits and batch builds split their per-nonce loops as the product's are split (add3_split.py, like_split.s)
 ADD3_LIKE_fast_first := $(FAST_SP)
 ADD3_LIKE_fast_hits := $(FAST_SP)
-$(BUILD)/fast_first_split.s $(BUILD)/fast_hits_split.s: $(FAST_SP) $(CSRC)/loop_mix.py
+ADD3_LIKE_fast_batch := $(FAST_SP)
+ADD3_LIKE_fast_batch_keep := $(FAST_SP)
+$(BUILD)/fast_first_split.s $(BUILD)/fast_hits_split.s $(BUILD)/fast_batch_split.s $(BUILD)/fast_batch_keep_split.s: $(FAST_SP) $(CSRC)/loop_mix.py
 $(FAST_NAMES:%=$(BUILD)/%_prio.s): $(BUILD)/%_prio.s: $(BUILD)/%_split.s $(CSRC)/issue_prio.py $(CSRC)/valu_rates.py
 	python3 $(CSRC)/issue_prio.py $< $@
 $(FAST_MIX): $(FAST_PS) $(CSRC)/loop_mix.py $(CSRC)/valu_rates.py
@@ -95,7 +103,7 @@ $(BUILD)/fast_search_nomarker.hsaco: $(FAST_PS)
 	grep -v mh_fast_queue_args $< > $(BUILD)/fast_search_nomarker.s
 	$(LLVM)/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=$(ARCH) -c -o $(BUILD)/fast_search_nomarker.o $(BUILD)/fast_search_nomarker.s
 	$(LLVM)/ld.lld -shared -o $@ $(BUILD)/fast_search_nomarker.o
-$(FAST_O): $(CSRC)/fast_co.S $(FAST_CO) $(FIRST_CO) $(HITS_CO)
+$(FAST_O): $(CSRC)/fast_co.S $(FAST_CO) $(FIRST_CO) $(HITS_CO) $(BATCH_CO)
 	gcc -c -fPIC -Wa,-I,$(BUILD) -o $@ $<
 
 # native C++ callers of the C-ABI (rpath: the library next to the package)

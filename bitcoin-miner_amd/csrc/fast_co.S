@@ -5,7 +5,9 @@
    (the same source with -DMH_FIRST through the same passes,
    build/fast_first.hsaco), loaded per device by the first mh_search_first,
    and the hits kernels of mh_search_hits (-DMH_HITS, build/fast_hits.hsaco),
-   loaded per device by the first mh_search_hits. */
+   loaded per device by the first mh_search_hits, and the batch kernels of
+   mh_search_batch_ex (-DMH_BATCH, build/fast_batch.hsaco), loaded per device
+   by the first such call that fuses a fast piece. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -31,4 +33,12 @@ mh_hits_co_begin:
     .globl mh_hits_co_end
 mh_hits_co_end:
     .size mh_hits_co_begin, mh_hits_co_end - mh_hits_co_begin
+    .p2align 12
+    .globl mh_batch_co_begin
+    .type mh_batch_co_begin, @object
+mh_batch_co_begin:
+    .incbin "fast_batch.hsaco"
+    .globl mh_batch_co_end
+mh_batch_co_end:
+    .size mh_batch_co_begin, mh_batch_co_end - mh_batch_co_begin
     .section .note.GNU-stack,"",@progbits

@@ -22,6 +22,9 @@
 // second code object that mh_search_first loads; without it nothing below differs from before.
 // -DMH_HITS builds the hits kernels hits_scan<J, MODE> (build/fast_hits.hsaco, through the same
 // passes), a third embedded code object that mh_search_hits loads; likewise.
+// -DMH_BATCH builds batch_fast<J, MODE> (build/fast_batch.hsaco, through the same passes; DESIGN.md
+// §3): the same chunk body, one workgroup per chunk of a table of many requests' pieces, a fourth
+// embedded code object that mh_search_batch_ex loads; likewise (with -DMH_HASH_KEEP: its test variant).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -566,6 +569,32 @@ __device__ __forceinline__ uint32_t claim_chunk(uint32_t* counter) {
     return blk;
 }
 
+#ifdef MH_BATCH
+// ---------------------------------------------------------------------------
+// batch_fast<J, MODE>: the fast pieces of many requests in one launch, for
+// mh_search_batch_ex(MH_BATCH_FUSE_FAST)
+// ---------------------------------------------------------------------------
+// Static grid, one workgroup per chunk of the launch: workgroup b reads its item's index from the
+// host's per-chunk table through readfirstlane, so the item's FastArgs are scalar loads, and runs
+// chunk b - chunk0 of that item into partials[slot0 + b - chunk0] (layout.hpp BatchFastItem; the
+// host checks every chunk, item and slot before the launch).  No atomics, no counter and no
+// dependency between workgroups: the grid always drains.  The chunk body reads its arguments
+// through a constant-address-space pointer laundered before the call, as fast_search's loop does:
+// the tables are written by the pass's one copy before the launch and by nothing after it.
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_fast(const BatchFastItem* __restrict__ items,
+                                                                          const uint32_t* __restrict__ chunk_item,
+                                                                          Partial* __restrict__ partials) {
+    using KItem = __attribute__((address_space(4))) const BatchFastItem;
+    const uint32_t b = blockIdx.x;
+    const uint32_t ii = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk_item[b]);
+    KItem* k = (KItem*)(items + ii);
+    asm volatile("" : "+s"(k));
+    const uint32_t chunk0 = k->chunk0, slot0 = k->slot0;
+    asm volatile("" : "+s"(k));
+    fast_chunk<J, MODE>(((const BatchFastItem*)k)->args, partials + slot0, b - chunk0);
+}
+#else
 #ifndef MH_FIRST
 template <int J, int MODE>
 #ifdef MH_HITS
@@ -678,6 +707,7 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void first_scan(
     }
 }
 #endif
+#endif  // MH_BATCH
 
 // Marker of a code object whose fast_search kernels run the work-queue loop above over this
 // FastArgs layout: its size is sizeof(FastArgs).  The library uses the work queue with a code
@@ -685,7 +715,13 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void first_scan(
 // embedded object always does; one loaded by the dev build's MINEHIP_DEV_CODE_OBJECT hook from
 // older sources runs one workgroup per chunk instead of searching only its first chunks.
 extern "C" {
+#ifdef MH_BATCH
+// Marker of the batch code object instead: its kernels read BatchFastItems of this size (the
+// library launches batch_fast only from a code object that carries it, search_kernels.hip).
+__device__ __attribute__((used)) uint8_t mh_fast_batch_items[sizeof(BatchFastItem)];
+#else
 __device__ __attribute__((used)) uint8_t mh_fast_queue_args[sizeof(FastArgs)];
+#endif
 #ifdef MH_HASH_KEEP
 // Marker of the coarse-hash variant: its kernels mask (H0, H1) by FastArgs::pad_.  The dev build
 // runs a search with MINEHIP_DEV_HASH_KEEP set only on a code object that carries it, so masked
@@ -700,6 +736,11 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 // 64..82), kModeTwo for J = 13..15 of block 0; the Early modes where a nonce
 // costs less with the digit ending word J innermost than with the last digit
 // in word J + 1 (plan.cpp: nonce_cost(J) < nonce_cost(J + 1)).
+#ifdef MH_BATCH
+#define MH_INST(j, m) \
+    template __global__ void batch_fast<j, m>(const BatchFastItem* __restrict__, const uint32_t* __restrict__, \
+                                              Partial* __restrict__);
+#else
 #ifndef MH_FIRST
 #ifdef MH_HITS
 #define MH_INST(j, m) \
@@ -711,6 +752,7 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 #define MH_INST(j, m) \
     template __global__ void first_scan<j, m>(const FastArgs, Partial* __restrict__, const FirstArgs);
 #endif
+#endif  // MH_BATCH
 MH_FAST_KERNELS(MH_INST)  // layout.hpp: the one list of instantiated layouts
 #undef MH_INST
 

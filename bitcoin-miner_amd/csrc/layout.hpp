@@ -181,12 +181,26 @@ constexpr uint32_t kBatchMaxEntries = 8192;   // entries of one pass
 
 // One generic piece of one request.  Its decades first/10 .. (first+count-1)/10 are cut into
 // tiles of kBatchTileDecades; tile tile0 + k of the pass runs decades k * kBatchTileDecades ..
-// of them and writes partials[slot0 + k].  Tiles are ordered by request, slot0 == tile0.
+// of them and writes partials[slot0 + k].  Tiles are ordered by request; slot0 == tile0 unless the
+// pass also holds fast pieces (BatchFastItem below), whose chunks take slots between the tiles'.
 struct BatchEntry {
     GenArgs g;            // mid, tail, plen, t; first / count: the entry's nonces
     uint32_t tile0;       // first tile of the entry in its pass
     uint32_t slot0;       // first partial slot of the entry in its pass
 };
+
+// ---- fused fast pieces of a batch (batch_fast<J, MODE> of build/fast_batch.hsaco) ----
+// One fast piece of one request of a pass of mh_search_batch_ex(MH_BATCH_FUSE_FAST).  The pieces of
+// one layout (J, MODE) share a launch of batch_fast<J, MODE> with a static grid, one workgroup per
+// 256-run chunk: workgroup b of the launch runs chunk b - chunk0 of the item chunk_item[b] names
+// and writes partials[slot0 + b - chunk0].  args.counter is null and args.n_chunks the item's chunks.
+constexpr uint32_t kBatchMaxFastItems = 1024;  // fast pieces of one pass
+struct BatchFastItem {
+    FastArgs args;
+    uint32_t chunk0;      // first chunk of the item in its launch
+    uint32_t slot0;       // first partial slot of the item in its pass
+};
+static_assert(sizeof(BatchFastItem) % 16 == 0, "items are laid out back to back in the pass's tables");
 
 // ---- batched first-hit search (batch_scan_first / merge_segments_first) ----
 // The device words of one request of a pass, in a table parallel to the segments; BatchEntry stays

@@ -59,6 +59,7 @@ def inner_loop(body):
 FAST = re.compile(r"^_ZN2mh11fast_searchILi(\d+)ELi(\d+)EE")
 FIRST = re.compile(r"^_ZN2mh10first_scanILi(\d+)ELi(\d+)EE")  # the -DMH_FIRST build's kernels (build/fast_first_prio.s)
 HITS = re.compile(r"^_ZN2mh9hits_scanILi(\d+)ELi(\d+)EE")  # the -DMH_HITS build's kernels (build/fast_hits_prio.s)
+BATCH = re.compile(r"^_ZN2mh10batch_fastILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH builds' kernels (build/fast_batch*_prio.s)
 
 
 def loop_mix(text, pattern=FAST):

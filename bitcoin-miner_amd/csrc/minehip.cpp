@@ -56,6 +56,13 @@ hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_ent
                              hipStream_t s);
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
                                  hipStream_t s);
+hipError_t launch_batch_scan_slots(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials,
+                                   uint32_t tiles, hipStream_t s);
+hipError_t launch_batch_fast(int dev, int J, int mode, const BatchFastItem* items, const uint32_t* chunk_item,
+                             Partial* partials, uint32_t chunks, hipStream_t s);
+#ifdef MH_DEV_HOOKS
+hipError_t batch_fast_hooks(int dev, uint64_t x, hipStream_t s, bool* keep_ok, bool* xor_ok);
+#endif
 hipError_t launch_batch_scan_first(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
                                    const uint32_t* order, BatchFirstWords* words, Partial* partials, uint32_t tiles,
                                    hipStream_t s);
@@ -325,9 +332,8 @@ bool coarse_piece(const mh::Piece& p, const mh::PlanOpts& opt) { return p.kind =
 // before it inside word J: the kernel adds every group digit into word J, so a digit elsewhere
 // would be hashed at the wrong place.  make_fast_args only builds such pieces; this re-checks it
 // where a piece reaches the kernel, with the U digits' hole inside the d digits.
-bool early_piece_ok(const mh::Piece& p) {
-    const mh::FastArgs& a = p.fa;
-    const uint32_t J = (uint32_t)p.J;
+bool early_piece_ok(const mh::FastArgs& a, int word) {
+    const uint32_t J = (uint32_t)word;
     if ((a.inner >> 2) != J || a.hole + a.hole_w > a.n_hi + a.L) return false;
     for (uint32_t j = 0; j + 1u < a.L; ++j) {
         const uint32_t pos = a.g_last - j - (j >= a.g_hole ? 1u : 0u);
@@ -347,7 +353,7 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
         // partials buffer holds one slot per block
         if (p.fa.n_runs == 0 || p.fa.L < 1 || p.fa.L > 5 || p.fa.n_hi + p.fa.L > 20)
             return fail(MH_EINTERNAL, "internal: bad fast piece");
-        if (p.fa.mode >= mh::kModeOneEarly && !early_piece_ok(p))
+        if (p.fa.mode >= mh::kModeOneEarly && !early_piece_ok(p.fa, p.J))
             return fail(MH_EINTERNAL, "internal: bad Early piece (an enumerated digit outside word J)");
         blocks = (p.fa.n_runs + mh::kBlockThreads - 1) / mh::kBlockThreads;
     } else {
@@ -869,6 +875,159 @@ int batch_run_fused(int dev, const mh::BatchRequest* reqs, const std::vector<mh:
     return rc;
 }
 
+// ---- batched search with fused fast pieces (mh_search_batch_ex) ----
+
+//   MINEHIP_BATCH_FAST_MAX    most nonces of a request mh_search_batch_ex(MH_BATCH_FUSE_FAST) fuses
+//                             (default kBatchFastMaxNonces; 0: no request with a fast piece is fused)
+//   MINEHIP_BATCH_FAST_LANES  "shared": the batch-aware lane rule (plan.hpp batch_min_lanes), which the
+//                             measurement did not favour; otherwise every request
+//                             keeps the lanes of its own mh_search plan (default)
+// (tests and tools/batch_fast_latency.py; the results never depend on them)
+uint64_t batch_fast_max() {
+    if (const char* e = getenv("MINEHIP_BATCH_FAST_MAX"))
+        if (*e) return strtoull(e, nullptr, 10);
+    return mh::kBatchFastMaxNonces;
+}
+bool batch_fast_shared_lanes() {
+    const char* e = getenv("MINEHIP_BATCH_FAST_LANES");
+    return e && strcmp(e, "shared") == 0;
+}
+
+// batch_run_pass for a pass that may hold fast pieces: one H2D copy of all its tables (entries,
+// segments, per-tile entry, fast items, per-chunk item), batch_scan_slots for the generic entries,
+// one batch_fast<J, MODE> launch per layout present, merge_segments, one D2H copy.  The fast
+// launches count in the fast class of the profile: per piece its nonces, ops and slots under its
+// (J, MODE, L); a launch's time under the (J, MODE, L) of its first, longest-lane piece.
+int batch_run_pass_ex(DevCtx* c, const mh::BatchRequest* reqs, const std::vector<mh::BatchPiece>& pieces,
+                      const mh::BatchTables& t, const mh::BatchFastTables& f, uint32_t slot_cap, BatchPending* pend,
+                      mh_result* out) {
+    if (!mh::batch_tables_ex_ok(t, f, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+    for (size_t k = 0; k < f.items.size(); ++k) {
+        const mh::BatchPiece& p = pieces[f.piece[k]];
+        if (f.items[k].args.mode >= mh::kModeOneEarly && !early_piece_ok(f.items[k].args, p.J))
+            return fail(MH_EINTERNAL, "internal: bad Early piece (an enumerated digit outside word J)");
+    }
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t ni = f.items.size(), chunks = f.chunk_item.size();
+    const size_t o_seg = align16(ne * sizeof(mh::BatchEntry)), o_tile = o_seg + align16((nreq + 1u) * sizeof(uint32_t));
+    const size_t o_item = o_tile + align16(tiles * sizeof(uint32_t)), o_chunk = o_item + ni * sizeof(mh::BatchFastItem);
+    const size_t bytes = o_chunk + align16(chunks * sizeof(uint32_t));
+    if (bytes > kBatchTableBytes || nreq > kBatchResults) return fail(MH_EINTERNAL, "internal: batch pass too large");
+    if (pend->toff + bytes > kBatchTableBytes || pend->req_idx.size() + nreq > kBatchResults ||
+        (c->prof && c->used + 1 + (int)f.launches.size() > kEventPairs)) {
+        const int rc = batch_drain(c, reqs, pend, out);
+        if (rc) return rc;
+    }
+    uint8_t* h = c->h_btab + pend->toff;
+    uint8_t* d = c->d_btab + pend->toff;
+    memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+    memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    memcpy(h + o_item, f.items.data(), ni * sizeof(mh::BatchFastItem));
+    memcpy(h + o_chunk, f.chunk_item.data(), chunks * sizeof(uint32_t));
+#ifdef MH_DEV_HOOKS
+    for (size_t i = 0; i < ne; ++i) ((mh::BatchEntry*)h)[i].g.pad = c->keep;
+    for (size_t i = 0; i < ni; ++i) ((mh::BatchFastItem*)(h + o_item))[i].args.pad_ = c->keep;
+#endif
+    MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    if (tiles) {
+        Timed* tm = nullptr;
+        if (c->prof) {  // generic class, as batch_run_pass
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 1;
+            tm->var = 0;
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_scan_slots((const mh::BatchEntry*)d, (const uint32_t*)(d + o_tile), c->d_partials,
+                                           (uint32_t)tiles, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[4] += t.nonces;
+        }
+    }
+    for (const mh::BatchFastLaunch& l : f.launches) {
+        Timed* tm = nullptr;
+        if (c->prof) {
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 0;
+            tm->var = var_index(l.J, l.mode, (int)f.items[l.item0].args.L);
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_fast(c->dev, l.J, l.mode, (const mh::BatchFastItem*)(d + o_item),
+                                     (const uint32_t*)(d + o_chunk) + l.chunk0, c->d_partials, l.chunks, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[0] += 1;
+            c->var[tm->var].launches += 1;
+            for (uint32_t k = l.item0; k < l.item0 + l.items; ++k) {
+                const mh::BatchPiece& p = pieces[f.piece[k]];
+                c->cnt[1] += p.count;
+                c->cnt[3] += p.count * (uint64_t)p.ops;
+                c->cnt[6] += p.count * (uint64_t)p.nslots;
+                VarStat& v = c->var[var_index(p.J, p.mode, p.L)];
+                v.nonces += p.count;
+                v.ops += p.count * (uint64_t)p.ops;
+                v.slots += p.count * (uint64_t)p.nslots;
+            }
+        }
+    }
+    const size_t roff = pend->req_idx.size();
+    MH_HIP(mh::launch_merge_segments(c->d_partials, (const uint32_t*)(d + o_seg), c->d_bres + roff, (uint32_t)nreq,
+                                     c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_bres + roff, c->d_bres + roff, nreq * sizeof(Partial), hipMemcpyDeviceToHost, c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    pend->toff += bytes;
+    return MH_OK;
+}
+
+// The fused passes of mh_search_batch_ex(MH_BATCH_FUSE_FAST), under the device's lock.
+int batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const std::vector<mh::BatchPiece>& pieces,
+                       const std::vector<mh::FastArgs>& args, int passes, uint32_t slot_cap, mh_result* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (rc) return rc;
+#ifdef MH_DEV_HOOKS
+    rc = read_hash_keep(c);
+    if (rc) return rc;
+    rc = read_hash_xor(c);
+    if (rc) return rc;
+    const bool any_fast = std::any_of(pieces.begin(), pieces.end(), [](const mh::BatchPiece& p) { return p.kind == 2; });
+    if (any_fast && (c->keep || c->xor_on)) {  // the hooks of the batch code object, as enqueue_piece's of the product's
+        uint64_t x = 0;
+        if (const char* e = getenv("MINEHIP_DEV_HASH_XOR")) x = strtoull(e, nullptr, 16);  // read_hash_xor accepted it
+        bool keep_ok = false, xor_ok = false;
+        MH_HIP(mh::batch_fast_hooks(c->dev, x, c->stream, &keep_ok, &xor_ok));
+        if (c->keep && !keep_ok)
+            return fail(MH_EINVAL, "MINEHIP_DEV_HASH_KEEP is set but the batch code object is not the coarse-hash "
+                                   "variant (MINEHIP_DEV_BATCH_CODE_OBJECT=build/fast_batch_keep.hsaco)");
+        if (c->xor_on && !xor_ok)
+            return fail(MH_EINVAL, "MINEHIP_DEV_HASH_XOR is set but the batch code object has no mh_dev_hash_xor "
+                                   "(MINEHIP_DEV_BATCH_CODE_OBJECT=build/fast_batch_keep.hsaco)");
+    } else if (any_fast) {  // off: a variant code object's word may still hold an earlier call's constant
+        bool keep_ok = false, xor_ok = false;
+        if (getenv("MINEHIP_DEV_BATCH_CODE_OBJECT")) MH_HIP(mh::batch_fast_hooks(c->dev, 0, c->stream, &keep_ok, &xor_ok));
+    }
+#endif
+    BatchPending pend;
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    for (int p = 0; p < passes && !rc; ++p) {
+        mh::build_batch_tables_ex(reqs, pieces, args, p, &t, &f);
+        // a pass without a fast piece is mh_search_batch's own pass (slot0 == tile0 throughout)
+        rc = f.items.empty() ? batch_run_pass(c, reqs, t, slot_cap, &pend, out)
+                             : batch_run_pass_ex(c, reqs, pieces, t, f, slot_cap, &pend, out);
+    }
+    if (!rc) rc = batch_drain(c, reqs, &pend, out);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
 // A fallback request's search: (request, hash, nonce) -> MH_*.
 using BatchFallback = std::function<int(const mh::BatchRequest&, uint64_t*, uint64_t*)>;
 
@@ -1371,6 +1530,79 @@ int mh_search_batch(int dev, const mh_request* reqs, size_t n, mh_result* out) {
     });
 }
 
+int mh_search_batch_ex(int dev, const mh_request* reqs, size_t n, uint32_t flags, mh_result* out) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (!(flags & MH_BATCH_FUSE_FAST)) return mh_search_batch(dev, reqs, n, out);
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    batch_requests(reqs, n, &status, &valid);
+    for (size_t i = 0; i < n; ++i) out[i] = mh_result{status[i], 0, 0, 0};
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(valid.data(), valid.size(), plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(),
+                      &pieces, &args);
+    int passes = 0;
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
+    if (passes) {
+        const int rc = batch_run_fused_ex(dev, valid.data(), pieces, args, passes, slot_cap, out);
+        if (rc) return rc;
+    }
+    for (const mh::BatchPiece& p : pieces) {  // the fallbacks, after the fused passes
+        if (p.kind != 1) continue;
+        const mh::BatchRequest& r = valid[p.idx];
+        const int rc = search_impl(dev, r.pre, r.lower, r.upper, &out[r.id].hash, &out[r.id].nonce);
+        if (rc) return rc;
+    }
+    return MH_OK;
+}
+
+int64_t mh_batch_plan_ex(const mh_request* reqs, size_t n, uint32_t flags, mh_batch_piece* out, int64_t cap) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (n == 0) return 0;
+    if (!reqs) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<mh::BatchRequest> all(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int rc = check_common(reqs[i].msg, reqs[i].len);
+        if (rc) return rc;
+        if (reqs[i].lower > reqs[i].upper) return fail(MH_ERANGE, "lower > upper");
+        mh::absorb_prefix(reqs[i].msg, reqs[i].len, &all[i].pre);
+        all[i].lower = reqs[i].lower;
+        all[i].upper = reqs[i].upper;
+        all[i].id = i;
+    }
+    int64_t k = 0;
+    if (!(flags & MH_BATCH_FUSE_FAST)) {  // mh_batch_plan's plan in the new struct
+        std::vector<mh::BatchItem> items;
+        mh::plan_batch(all.data(), n, plan_opts(), batch_slots(), &items);
+        for (const mh::BatchItem& it : items) {
+            if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+            if (out) out[k] = mh_batch_piece{it.req, it.first, it.count, it.kind, it.pass, it.slot, it.slots, 0, 0, 0, -1};
+            ++k;
+        }
+        return k;
+    }
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(all.data(), n, plan_opts(), batch_slots(), batch_fast_shared_lanes(), batch_fast_max(), &pieces,
+                      &args);
+    for (const mh::BatchPiece& p : pieces) {
+        if (k >= cap) return cap + 1;
+        if (out)
+            out[k] = mh_batch_piece{p.req, p.first, p.count, p.kind, p.pass, p.slot, p.slots, p.J, p.mode, p.L, p.launch};
+        ++k;
+    }
+    return k;
+}
+
 int64_t mh_batch_plan(const mh_request* reqs, size_t n, mh_batch_item* out, int64_t cap) {
     g_err.clear();
     if (n == 0) return 0;
@@ -1705,7 +1937,9 @@ int mh_profile_kernels(int dev, mh_kernel_stat* out, int cap) {
     int n = 0;
     for (int i = 0; i < kVariants; ++i) {
         const VarStat& v = c->var[i];
-        if (!v.launches) continue;
+        // (a fused batch launch of mixed lane lengths counts under its first piece's L, the
+        // other pieces' nonces under theirs, with no launch of their own)
+        if (!v.launches && !v.nonces) continue;
         if (n < cap) {
             out[n].word = i % 16;
             out[n].mode = (i / 16) % mh::kModes;

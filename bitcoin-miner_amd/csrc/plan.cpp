@@ -651,6 +651,287 @@ bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap) {
     return true;
 }
 
+// ---- batched search with fused fast pieces ----
+
+uint64_t batch_min_lanes(uint64_t min_lanes, size_t fast_requests) {
+    if (fast_requests < 2) return min_lanes;
+    uint64_t share = min_lanes / fast_requests, p = 1;
+    while (p <= share / 2u) p *= 2u;  // the largest power of two <= share (1 for share <= 1)
+    share = std::max<uint64_t>(p, (uint64_t)kBlockThreads);  // at least one chunk's runs
+    return std::min(min_lanes, share);  // never more than the caller's own
+}
+
+void plan_batch_ex(const BatchRequest* reqs, size_t n, const PlanOpts& opt, uint32_t slot_cap, bool shared_lanes,
+                   uint64_t max_nonces, std::vector<BatchPiece>* pieces, std::vector<FastArgs>* args) {
+    pieces->clear();
+    args->clear();
+    slot_cap = std::min(slot_cap, kMaxBlocksPerLaunch);
+    // One request's plan under o: its pieces if they fit a pass (fused), and whether it holds a
+    // fast piece at all.  may_fast false (over the size cap): a fast piece makes it a fallback.
+    struct One {
+        bool fused = true, saw_fast = false;
+        uint64_t slots = 0;
+        uint32_t entries = 0, fast = 0;
+        std::vector<BatchPiece> pieces;
+        std::vector<FastArgs> args;
+    };
+    auto plan_one = [&](size_t i, const PlanOpts& o, bool may_fast, One* out) {
+        const BatchRequest& r = reqs[i];
+        *out = One();
+        plan_search(r.pre, r.lower, r.upper, o, [&](const Piece& p) {
+            BatchPiece b;
+            memset(&b, 0, sizeof b);
+            b.req = r.id;
+            b.first = p.first;
+            b.count = p.count;
+            b.launch = -1;
+            b.idx = i;
+            if (p.kind == 1) {
+                if (out->entries == kBatchMaxEntries) return out->fused = false;
+                ++out->entries;
+                b.kind = 0;
+                b.slots = (uint32_t)std::min<uint64_t>(batch_tiles(p.first, p.count), (uint64_t)slot_cap + 1u);
+            } else {
+                out->saw_fast = true;
+                if (!may_fast || out->fast == kBatchMaxFastItems) return out->fused = false;
+                ++out->fast;
+                b.kind = 2;
+                b.slots = (p.fa.n_runs + (uint32_t)kBlockThreads - 1u) / (uint32_t)kBlockThreads;
+                b.J = p.J;
+                b.mode = p.mode;
+                b.L = p.L;
+                b.ops = p.ops;
+                b.nslots = p.slots;
+                b.fa = out->args.size();
+                out->args.push_back(p.fa);
+                out->args.back().n_chunks = b.slots;
+                out->args.back().counter = nullptr;
+            }
+            out->slots += b.slots;
+            if (out->slots > slot_cap) return out->fused = false;
+            out->pieces.push_back(b);
+            return true;
+        });
+    };
+    // every request under its own plan first: the generic-only ones are done with it, and the
+    // candidates -- a fast piece in the own plan, no more nonces than the cap -- are counted
+    std::vector<One> one(n);
+    std::vector<char> cand(n, 0);
+    size_t ncand = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const BatchRequest& r = reqs[i];
+        const bool over = r.upper - r.lower >= max_nonces;  // count - 1; the whole of u64 included
+        plan_one(i, opt, !over, &one[i]);
+        if (over) continue;
+        if (!one[i].fused && !one[i].saw_fast)  // stopped for its size before a fast piece: look on
+            plan_search(r.pre, r.lower, r.upper, opt, [&](const Piece& p) { return !(one[i].saw_fast = p.kind == 0); });
+        if (one[i].saw_fast) cand[i] = 1, ++ncand;
+    }
+    PlanOpts shared = opt;
+    if (shared_lanes) shared.min_lanes = batch_min_lanes(opt.min_lanes, ncand);
+    if (shared.min_lanes != opt.min_lanes)
+        for (size_t i = 0; i < n; ++i)
+            if (cand[i]) plan_one(i, shared, true, &one[i]);
+
+    int pass = 0;
+    uint32_t used_slots = 0, used_reqs = 0, used_entries = 0, used_fast = 0;
+    std::vector<size_t> pass_fast; // the fast pieces (indices into *pieces) of the pass being packed
+    // launches and chunk offsets of a finished pass: groups in order of first appearance, inside a
+    // group L descending, then request order (the order the pieces were planned in)
+    auto close_pass = [&]() {
+        std::vector<std::pair<int, int>> groups;
+        for (size_t k : pass_fast) {
+            const std::pair<int, int> g{(*pieces)[k].J, (*pieces)[k].mode};
+            if (std::find(groups.begin(), groups.end(), g) == groups.end()) groups.push_back(g);
+        }
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            std::vector<size_t> in;
+            for (size_t k : pass_fast)
+                if ((*pieces)[k].J == groups[gi].first && (*pieces)[k].mode == groups[gi].second) in.push_back(k);
+            std::stable_sort(in.begin(), in.end(), [&](size_t a, size_t b) { return (*pieces)[a].L > (*pieces)[b].L; });
+            uint32_t chunk = 0;
+            for (size_t k : in) {
+                (*pieces)[k].launch = (int)gi;
+                (*pieces)[k].chunk0 = chunk;
+                chunk += (*pieces)[k].slots;
+            }
+        }
+        pass_fast.clear();
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const BatchRequest& r = reqs[i];
+        const One& o = one[i];
+        if (!o.fused) {
+            BatchPiece b;
+            memset(&b, 0, sizeof b);
+            b.req = r.id;
+            b.first = r.lower;
+            b.count = r.upper - r.lower + 1u;
+            b.kind = 1;
+            b.pass = b.launch = -1;
+            b.idx = i;
+            pieces->push_back(b);
+            continue;
+        }
+        if (used_reqs && (used_slots + o.slots > slot_cap || used_reqs == kBatchMaxRequests ||
+                          used_entries + o.entries > kBatchMaxEntries || used_fast + o.fast > kBatchMaxFastItems)) {
+            close_pass();
+            ++pass;
+            used_slots = used_reqs = used_entries = used_fast = 0;
+        }
+        for (BatchPiece b : o.pieces) {
+            b.pass = pass;
+            b.slot = used_slots;
+            used_slots += b.slots;
+            if (b.kind == 2) {
+                pass_fast.push_back(pieces->size());
+                args->push_back(o.args[b.fa]);
+                b.fa = args->size() - 1u;
+            }
+            pieces->push_back(b);
+        }
+        ++used_reqs;
+        used_entries += o.entries;
+        used_fast += o.fast;
+    }
+    close_pass();
+}
+
+void build_batch_tables_ex(const BatchRequest* reqs, const std::vector<BatchPiece>& pieces,
+                           const std::vector<FastArgs>& args, int pass, BatchTables* t, BatchFastTables* f) {
+    t->entries.clear();
+    t->tile_entry.clear();
+    t->seg.clear();
+    t->req_idx.clear();
+    t->nonces = 0;
+    f->items.clear();
+    f->chunk_item.clear();
+    f->launches.clear();
+    f->piece.clear();
+    uint32_t slots = 0;
+    std::vector<size_t> fast;  // the pass's fast pieces
+    bool any = false;
+    size_t last_idx = 0;
+    for (size_t k = 0; k < pieces.size(); ++k) {
+        const BatchPiece& p = pieces[k];
+        if (p.kind == 1 || p.pass != pass) continue;
+        if (!any || last_idx != p.idx) {
+            t->req_idx.push_back(p.idx);
+            t->seg.push_back(p.slot);
+            any = true;
+            last_idx = p.idx;
+        }
+        if (p.kind == 0) {
+            BatchEntry e;
+            make_gen_args(reqs[p.idx].pre, &e.g);
+            e.g.first = p.first;
+            e.g.count = p.count;
+            e.tile0 = (uint32_t)t->tile_entry.size();
+            e.slot0 = p.slot;
+            t->tile_entry.insert(t->tile_entry.end(), p.slots, (uint32_t)t->entries.size());
+            t->entries.push_back(e);
+            t->nonces += p.count;
+        } else {
+            fast.push_back(k);
+        }
+        slots = p.slot + p.slots;
+    }
+    t->seg.push_back(slots);
+    // items in launch order, then chunk order (plan_batch_ex numbered both)
+    std::stable_sort(fast.begin(), fast.end(), [&](size_t a, size_t b) {
+        return pieces[a].launch != pieces[b].launch ? pieces[a].launch < pieces[b].launch
+                                                    : pieces[a].chunk0 < pieces[b].chunk0;
+    });
+    for (size_t k : fast) {
+        const BatchPiece& p = pieces[k];
+        if (f->launches.empty() || (int)f->launches.size() - 1 != p.launch)
+            f->launches.push_back(BatchFastLaunch{p.J, p.mode, (uint32_t)f->items.size(), 0u,
+                                                  (uint32_t)f->chunk_item.size(), 0u});
+        BatchFastLaunch& l = f->launches.back();
+        BatchFastItem it;
+        it.args = args[p.fa];
+        it.chunk0 = p.chunk0;
+        it.slot0 = p.slot;
+        f->chunk_item.insert(f->chunk_item.end(), p.slots, (uint32_t)f->items.size());
+        f->items.push_back(it);
+        f->piece.push_back(k);
+        l.items += 1u;
+        l.chunks += p.slots;
+    }
+}
+
+bool batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, uint32_t slot_cap) {
+    const size_t tiles = t.tile_entry.size(), chunks = f.chunk_item.size(), nreq = t.req_idx.size();
+    const size_t slots = tiles + chunks;
+    if (slots == 0 || slots > slot_cap || slots > kMaxBlocksPerLaunch) return false;
+    if (t.entries.size() > kBatchMaxEntries || t.entries.size() > tiles || (tiles && t.entries.empty())) return false;
+    if (f.items.size() > kBatchMaxFastItems || f.items.size() > chunks || (chunks && f.items.empty())) return false;
+    if (nreq == 0 || nreq > kBatchMaxRequests || nreq > slots || t.seg.size() != nreq + 1u) return false;
+    std::vector<uint8_t> written(slots, 0);  // per slot: tiles and chunks that write it
+    auto write = [&](uint64_t slot) {
+        if (slot >= slots || written[(size_t)slot]) return false;
+        written[(size_t)slot] = 1;
+        return true;
+    };
+    // entries: in tile order, each with exactly its tiles, together all tiles
+    uint64_t next = 0;
+    for (const BatchEntry& e : t.entries) {
+        if (e.g.count == 0 || e.g.first + (e.g.count - 1u) < e.g.first || e.g.t > 63u) return false;
+        if (e.tile0 != next) return false;
+        next += batch_tiles(e.g.first, e.g.count);
+        if (next > tiles) return false;
+    }
+    if (next != tiles) return false;
+    // tiles: each inside its entry's tiles, writing a slot of its own
+    for (size_t i = 0; i < tiles; ++i) {
+        const uint32_t ei = t.tile_entry[i];
+        if (ei >= t.entries.size()) return false;
+        const BatchEntry& e = t.entries[ei];
+        if (i < e.tile0 || i - e.tile0 >= batch_tiles(e.g.first, e.g.count)) return false;
+        if (!write((uint64_t)e.slot0 + (i - e.tile0))) return false;
+    }
+    // launches: together all items and all chunks, in order; every item of its launch's layout, its
+    // chunks exactly its runs' and behind the launch's earlier items'
+    uint64_t item = 0, chunk = 0;
+    for (const BatchFastLaunch& l : f.launches) {
+        if (!fast_kernel_exists(l.J, l.mode) || l.items == 0 || l.chunks == 0) return false;
+        if (l.item0 != item || l.chunk0 != chunk) return false;
+        item += l.items;
+        chunk += l.chunks;
+        if (item > f.items.size() || chunk > chunks) return false;
+        uint64_t c = 0;
+        for (uint32_t k = l.item0; k < l.item0 + l.items; ++k) {
+            const BatchFastItem& it = f.items[k];
+            const FastArgs& a = it.args;
+            if (a.mode != (uint32_t)l.mode || a.counter != nullptr || a.n_runs == 0 || a.L < 1 || a.L > 5 ||
+                a.n_hi + a.L > 20)
+                return false;
+            if (a.n_chunks != (a.n_runs + (uint32_t)kBlockThreads - 1u) / (uint32_t)kBlockThreads) return false;
+            if (it.chunk0 != c) return false;
+            c += a.n_chunks;
+            if (c > l.chunks) return false;
+        }
+        if (c != l.chunks) return false;
+        // chunks: each names an item of this launch and lies inside that item's chunks
+        for (uint32_t b = 0; b < l.chunks; ++b) {
+            const uint32_t ii = f.chunk_item[l.chunk0 + b];
+            if (ii < l.item0 || ii >= l.item0 + l.items) return false;
+            const BatchFastItem& it = f.items[ii];
+            if (b < it.chunk0 || b - it.chunk0 >= it.args.n_chunks) return false;
+            if (!write((uint64_t)it.slot0 + (b - it.chunk0))) return false;
+        }
+    }
+    if (item != f.items.size() || chunk != chunks) return false;
+    // every slot written exactly once (none twice above; as many writers as slots)
+    for (uint8_t w : written)
+        if (!w) return false;
+    // segments: contiguous, non-empty, together all slots
+    if (t.seg.front() != 0 || t.seg.back() != slots) return false;
+    for (size_t r = 0; r < nreq; ++r)
+        if (t.seg[r] >= t.seg[r + 1]) return false;
+    return true;
+}
+
 // ---- batched first-hit search ----
 
 namespace {

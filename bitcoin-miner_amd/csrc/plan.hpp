@@ -201,6 +201,62 @@ void build_batch_tables(const BatchRequest* reqs, const std::vector<BatchItem>& 
 // non-empty and together all slots.
 bool batch_tables_ok(const BatchTables& t, uint32_t slot_cap);
 
+// ---- batched search with fused fast pieces (mh_search_batch_ex / mh_batch_plan_ex) ----
+// plan_batch with MH_BATCH_FUSE_FAST: a request whose plan holds fast pieces is fused too, while its
+// tiles and chunks fit one pass (slot_cap), its entries kBatchMaxEntries, its fast pieces
+// kBatchMaxFastItems, and its nonce count is at most max_nonces; anything else is a fallback.  A
+// fused request's pieces take one contiguous slot segment in nonce order: a generic piece
+// batch_tiles slots, a fast piece one slot per 256-run chunk.  The fast pieces of a pass are grouped
+// by layout (J, mode), one launch of batch_fast<J, mode> per group, the groups in the order their
+// layouts first appear; inside a launch the pieces are ordered longest lanes first (L descending,
+// then request order).
+// Lanes: every request keeps its own plan's (shared_lanes false, the library's default).  The
+// batch-aware rule (shared_lanes; MINEHIP_BATCH_FAST_LANES=shared) plans the candidates -- the
+// requests whose own plan (opt) holds a fast piece and which pass the size cap -- with min_lanes =
+// batch_min_lanes(opt.min_lanes, their number): the other requests of the call fill the device, so
+// a request could afford longer lanes than alone.  Measured, it did not win.
+constexpr uint64_t kBatchFastMaxNonces = 1000000000ull;  // default max_nonces, MH_BATCH_FAST_MAX_NONCES (measured)
+uint64_t batch_min_lanes(uint64_t min_lanes, size_t fast_requests);
+
+struct BatchPiece {
+    uint64_t req;           // BatchRequest::id
+    uint64_t first, count;  // the piece's nonces; fallback: the request's (count mod 2^64)
+    int kind;               // 0 fused generic entry, 1 fallback, 2 fused fast piece
+    int pass;               // fallback: -1
+    uint32_t slot, slots;   // first partial slot in the pass; tiles (kind 0) or chunks (kind 2)
+    int J, mode, L;         // kind 2; else 0
+    int launch;             // kind 2: its batch_fast launch within the pass; else -1
+    uint32_t chunk0;        // kind 2: its first chunk within that launch
+    size_t idx;             // position of the request in the array given to plan_batch_ex
+    uint32_t ops, nslots;   // kind 2: nonce_cost(J, mode)
+    size_t fa;              // kind 2: its launch arguments, args[fa] (counter null, n_chunks = slots)
+};
+void plan_batch_ex(const BatchRequest* reqs, size_t n, const PlanOpts& opt, uint32_t slot_cap, bool shared_lanes,
+                   uint64_t max_nonces, std::vector<BatchPiece>* pieces, std::vector<FastArgs>* args);
+
+// The device tables of one pass: BatchTables (entries with slot0 apart from tile0; seg over tiles
+// and chunks together), the fast items in launch order and, per launch, its chunks' items.
+struct BatchFastLaunch {
+    int J, mode;
+    uint32_t item0, items;    // its items in BatchFastTables::items
+    uint32_t chunk0, chunks;  // its part of BatchFastTables::chunk_item
+};
+struct BatchFastTables {
+    std::vector<BatchFastItem> items;
+    std::vector<uint32_t> chunk_item;  // per launch, per chunk: its item (index into items)
+    std::vector<BatchFastLaunch> launches;
+    std::vector<size_t> piece;         // per item: its BatchPiece (index into the plan)
+};
+void build_batch_tables_ex(const BatchRequest* reqs, const std::vector<BatchPiece>& pieces,
+                           const std::vector<FastArgs>& args, int pass, BatchTables* t, BatchFastTables* f);
+
+// What batch_scan, batch_fast and merge_segments rely on, checked before every launch of a pass:
+// every tile maps to an entry and lies inside its tiles, every chunk maps to an item of its launch's
+// layout and lies inside that item's n_chunks, every item's lanes cover exactly its runs, every slot
+// of every segment is written by exactly one tile or chunk, the segments are contiguous, non-empty
+// and together all slots, and nothing lies beyond slot_cap.
+bool batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, uint32_t slot_cap);
+
 // ---- batched first-hit search (mh_search_first_batch / mh_first_batch_order) ----
 // The tables batch_scan_first reads beside a pass's BatchTables (the plan does not depend on the
 // targets, so plan_batch and build_batch_tables serve unchanged).

@@ -37,6 +37,11 @@
 //                         whose hash is <= its request's target appended to the request's region
 //                         of the device hit buffer through a per-request cursor.
 //   merge_segments_hits   merge_segments, and the request's {hash, nonce, count} out.
+//   batch_fast<J, MODE>   (fast_search.hip, -DMH_BATCH) the fast pieces of many requests in one
+//                         launch, one workgroup per 256-run chunk of a table of items; a fourth
+//                         embedded code object, loaded by the first mh_search_batch_ex that fuses one.
+//   batch_scan_slots      batch_scan writing partials[slot0 + tile - tile0]: the generic entries of
+//                         a pass whose slot segments also hold fast chunks.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -61,6 +66,8 @@ extern "C" const unsigned char mh_fast_co_begin[];
 extern "C" const unsigned char mh_first_co_begin[];
 // the same source built with -DMH_HITS: hits_scan<J, MODE>, the fast kernels of mh_search_hits
 extern "C" const unsigned char mh_hits_co_begin[];
+// the same source built with -DMH_BATCH: batch_fast<J, MODE>, the fused fast pieces of mh_search_batch_ex
+extern "C" const unsigned char mh_batch_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -392,9 +399,11 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
 // writes partials[i].  The entry index comes from the host's per-tile table through
 // readfirstlane, so the entry's fields are scalar loads.  No atomics, no counters and no
 // dependency between workgroups: the grid always drains.
-__global__ __launch_bounds__(kBlockThreads) void batch_scan(const BatchEntry* __restrict__ entries,
-                                                            const uint32_t* __restrict__ tile_entry,
-                                                            Partial* __restrict__ partials) {
+// SLOTS: the tile writes partials[slot0 + tile - tile0] instead of partials[tile] (batch_scan_slots).
+template <bool SLOTS>
+__device__ __forceinline__ void batch_scan_tile(const BatchEntry* __restrict__ entries,
+                                                const uint32_t* __restrict__ tile_entry,
+                                                Partial* __restrict__ partials) {
     using namespace dev;
     const uint32_t ei = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_entry[blockIdx.x]);
     const BatchEntry& e = entries[ei];
@@ -416,7 +425,22 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan(const BatchEntry* __
         }
     }
     block_min(bh, bn);
-    if (threadIdx.x == 0) partials[blockIdx.x] = Partial{bh, bn};
+    if (threadIdx.x == 0) partials[SLOTS ? e.slot0 + (blockIdx.x - e.tile0) : blockIdx.x] = Partial{bh, bn};
+}
+
+__global__ __launch_bounds__(kBlockThreads) void batch_scan(const BatchEntry* __restrict__ entries,
+                                                            const uint32_t* __restrict__ tile_entry,
+                                                            Partial* __restrict__ partials) {
+    batch_scan_tile<false>(entries, tile_entry, partials);
+}
+
+// batch_scan for a pass of mh_search_batch_ex(MH_BATCH_FUSE_FAST): a request's slot segment holds
+// its tiles and its fast pieces' chunks in nonce order, so an entry's slots start at slot0, apart
+// from tile0 (the host checks that every slot has exactly one writer, plan.cpp batch_tables_ex_ok).
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_slots(const BatchEntry* __restrict__ entries,
+                                                                  const uint32_t* __restrict__ tile_entry,
+                                                                  Partial* __restrict__ partials) {
+    batch_scan_tile<true>(entries, tile_entry, partials);
 }
 
 // batch_scan for mh_search_first_batch: workgroup b runs tile order[b] -- the host's
@@ -651,15 +675,25 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // variant: kFastFirst, the first-hit kernels first_scan<J, MODE> of the second embedded code object
 // (module key ":first", no file of that name is ever loaded), or kFastHits, the hits kernels
 // hits_scan<J, MODE> of the third (":hits"); no hook replaces either
-enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2 };
+// or kFastBatch, batch_fast<J, MODE> of the fourth (":batch"; the dev build reads
+// MINEHIP_DEV_BATCH_CODE_OBJECT, a code object file to use instead: build/fast_batch_keep.hsaco)
+enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3 };
+#ifdef MH_DEV_HOOKS
+std::string batch_module_path() {
+    const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
+    return (co && *co) ? co : ":batch";
+}
+#else
+std::string batch_module_path() { return ":batch"; }
+#endif
 hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr,
                          FastVariant variant = kFastProduct) {
-    const bool first = variant == kFastFirst, hits = variant == kFastHits;
+    const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
-    const std::string path = first ? ":first" : hits ? ":hits" : (co && *co) ? co : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : (co && *co) ? co : "";
 #else
-    const std::string path = first ? ":first" : hits ? ":hits" : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
@@ -667,6 +701,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         hipModule_t m;
         const hipError_t e = first          ? hipModuleLoadData(&m, mh_first_co_begin)
                              : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
+                             : path == ":batch" ? hipModuleLoadData(&m, mh_batch_co_begin)
                              : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
                                             : hipModuleLoad(&m, path.c_str());
         if (e != hipSuccess) {
@@ -676,8 +711,11 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         it = g_mods.emplace(std::make_pair(path, dev), m).first;
         hipDeviceptr_t gp = nullptr;
         size_t gsz = 0;
-        const bool marked = hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_queue_args") == hipSuccess &&
-                            gsz == sizeof(FastArgs);
+        // (a batch code object: mh_fast_batch_items at sizeof(BatchFastItem), the table layout its kernels read)
+        const bool marked = batch ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_items") == hipSuccess &&
+                                        gsz == sizeof(BatchFastItem)
+                                  : hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_queue_args") == hipSuccess &&
+                                        gsz == sizeof(FastArgs);
         (void)hipGetLastError();
         g_queue_ok[m] = marked;
 #ifdef MH_DEV_HOOKS
@@ -699,6 +737,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         snprintf(name, sizeof name,
                  first  ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
+                 : batch ? "_ZN2mh10batch_fastILi%dELi%dEEEvPKNS_13BatchFastItemEPKjPNS_7PartialE"
                         : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
                  J, mode);
         hipFunction_t fn;
@@ -904,6 +943,56 @@ hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_ent
     hipLaunchKernelGGL(batch_scan, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, partials);
     return hipGetLastError();
 }
+
+// The generic entries of a pass that also holds fast pieces: batch_scan_slots.
+hipError_t launch_batch_scan_slots(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials,
+                                   uint32_t tiles, hipStream_t s) {
+    hipLaunchKernelGGL(batch_scan_slots, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, partials);
+    return hipGetLastError();
+}
+
+// One launch of batch_fast<J, mode> of the batch code object (loaded on dev, the current device, by
+// the first call): one workgroup per chunk, chunk_item[b] the item of chunk b (the caller has
+// checked the tables, minehip.cpp batch_run_pass_ex).  A code object without the table marker at
+// this library's sizeof(BatchFastItem) is refused.
+hipError_t launch_batch_fast(int dev, int J, int mode, const BatchFastItem* items, const uint32_t* chunk_item,
+                             Partial* partials, uint32_t chunks, hipStream_t s) {
+    if (!fast_variant_exists(J, mode) || chunks == 0 || chunks > kMaxBlocksPerLaunch) return hipErrorInvalidValue;
+    hipFunction_t fn;
+    bool marked = false;
+    const hipError_t e = fast_function(dev, J, mode, &fn, &marked, kFastBatch);
+    if (e != hipSuccess) return e;
+    if (!marked) return hipErrorInvalidImage;
+    void* params[] = {&items, &chunk_item, &partials};
+    return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+
+#ifdef MH_DEV_HOOKS
+// The hooks of the batch code object in use on dev (the current device; loaded if need be): whether
+// its kernels mask hashes by FastArgs::pad_ (*keep_ok), and x made its hash-XOR constant if it has
+// the word (*xor_ok), by a copy on s that has completed on return; the caller holds the device idle.
+hipError_t batch_fast_hooks(int dev, uint64_t x, hipStream_t s, bool* keep_ok, bool* xor_ok) {
+    hipFunction_t f;
+    *keep_ok = *xor_ok = false;
+    hipError_t e = fast_function(dev, 4, kModeOne, &f, nullptr, kFastBatch);
+    if (e != hipSuccess) return e;
+    const uint32_t w[2] = {(uint32_t)(x >> 32), (uint32_t)x};
+    std::lock_guard<std::mutex> g(g_mod_mu);
+    const auto it = g_mods.find({batch_module_path(), dev});
+    if (it == g_mods.end()) return hipSuccess;
+    *keep_ok = g_keep_ok[it->second];
+    hipDeviceptr_t gp = g_xor_ptr[it->second];
+    if (!gp) return hipSuccess;
+    *xor_ok = true;
+    if (g_xor_mod[it->second] != x) {
+        e = hipMemcpyHtoDAsync(gp, (void*)w, sizeof w, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        g_xor_mod[it->second] = x;
+    }
+    return hipSuccess;
+}
+#endif
 
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
                                  hipStream_t s) {

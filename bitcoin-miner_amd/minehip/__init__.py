@@ -7,7 +7,8 @@ tests read like the reference (line numbers into the reference repo):
   hash_batch(msg, nonces)    the same for many nonces
   search(msg, lower, upper)  the miner scan (stub miner.go:33)
   search_multi(...)          the scan sharded over several devices
-  search_batch(requests)     many small scans fused into one GPU pass
+  search_batch(requests)     many small scans fused into one GPU pass (fuse_fast=True: the
+                             fast pieces of larger ones too)
   search_first(msg, lower, upper, target)
                              the smallest nonce whose hash is <= target
   search_hits(msg, lower, upper, target, cap=4096)
@@ -29,6 +30,7 @@ from ._lib import lib, mh_piece, mh_message, mh_kernel_stat, mh_span, OPS_PER_BL
 from ._lib import MH_OK, MH_EINVAL, MH_ERANGE, MH_ETOOLONG, MH_ENODEV, MH_EHIP  # noqa: F401
 from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
 from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
+from ._lib import mh_batch_piece, MH_BATCH_FUSE_FAST, MH_BATCH_FAST_MAX_NONCES  # noqa: F401
 from ._lib import mh_first_request, mh_first_result  # noqa: F401
 from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP  # noqa: F401
 from ._lib import mh_hits_request, mh_hits_result, mh_hits_region  # noqa: F401
@@ -121,9 +123,11 @@ _REQUEST_ERRORS = {MH_EINVAL: "msg is NULL", MH_ERANGE: "lower > upper",
                    MH_ETOOLONG: "message longer than MH_MAX_MSG_LEN"}
 
 
-def search_batch(requests, dev=0, errors="raise"):
+def search_batch(requests, dev=0, errors="raise", fuse_fast=False):
     """[(hash, nonce), ...] of many (msg, lower, upper) requests, each exactly what search() gives,
-    with the small ones fused into one GPU pass (mh_search_batch).  A request that fails alone
+    with the small ones fused into one GPU pass (mh_search_batch).  fuse_fast=True also fuses the
+    fast pieces of the larger requests, up to MH_BATCH_FAST_MAX_NONCES nonces each
+    (mh_search_batch_ex with MH_BATCH_FUSE_FAST).  A request that fails alone
     (lower > upper, message too long) raises MinehipError naming its index, or with
     errors="return" leaves that MinehipError in its place in the list."""
     if errors not in ("raise", "return"):
@@ -131,7 +135,10 @@ def search_batch(requests, dev=0, errors="raise"):
     requests = list(requests)
     arr, keep = _requests(requests)
     out = (mh_result * max(1, len(requests)))()
-    _check(lib.mh_search_batch(dev, arr, len(requests), out))
+    if fuse_fast:
+        _check(lib.mh_search_batch_ex(dev, arr, len(requests), MH_BATCH_FUSE_FAST, out))
+    else:
+        _check(lib.mh_search_batch(dev, arr, len(requests), out))
     res = []
     for i in range(len(requests)):
         if out[i].status == MH_OK:
@@ -157,6 +164,23 @@ def batch_plan(requests, cap=1 << 16):
     if k > cap:
         raise ValueError("batch plan longer than cap")
     return [{f: getattr(buf[i], f) for f, _ in mh_batch_item._fields_} for i in range(k)]
+
+
+def batch_plan_ex(requests, fuse_fast=True, cap=1 << 16, flags=None):
+    """Host-only: how search_batch(fuse_fast=...) would run the requests -- one dict per piece of a
+    fused request (kind 0: a generic entry, its pass, first partial slot and tiles; kind 2: a fast
+    piece, its pass, first slot, chunks, layout word / mode / lo_digits and launch) and one per
+    fallback request (kind 1) (mh_batch_plan_ex; `flags` overrides the flag word)."""
+    requests = list(requests)
+    arr, keep = _requests(requests)
+    buf = (mh_batch_piece * cap)()
+    k = lib.mh_batch_plan_ex(arr, len(requests), (MH_BATCH_FUSE_FAST if fuse_fast else 0) if flags is None else flags,
+                             buf, cap)
+    if k < 0:
+        _check(k)
+    if k > cap:
+        raise ValueError("batch plan longer than cap")
+    return [{f: getattr(buf[i], f) for f, _ in mh_batch_piece._fields_} for i in range(k)]
 
 
 def search_first_batch(requests, dev=0, errors="raise"):

@@ -28,6 +28,8 @@ OPS_PER_BLOCK = 1376  # MH_OPS_PER_BLOCK
 MH_ABI_VERSION = 5    # include/minehip.h: the struct layouts below are this version's
 MH_MAX_WORKERS = 256  # most devices one mh_search_multi / mh_multi_plan call may list
 MH_HITS_MAX_CAP = 1 << 20  # most entries one mh_search_hits call returns
+MH_BATCH_FUSE_FAST = 1     # mh_search_batch_ex / mh_batch_plan_ex flag
+MH_BATCH_FAST_MAX_NONCES = 10 ** 9  # most nonces of a request MH_BATCH_FUSE_FAST fuses
 
 #: every symbol include/*.h declares
 EXPORTS = (
@@ -36,7 +38,7 @@ EXPORTS = (
     "mh_profile_enable", "mh_profile_read", "mh_profile_kernels", "mh_plan", "mh_multi_plan",
     "mh_multi_rates", "mh_search_batch", "mh_batch_plan", "mh_miner_handle_batch",
     "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
-    "mh_search_hits_batch", "mh_hits_batch_regions",
+    "mh_search_hits_batch", "mh_hits_batch_regions", "mh_search_batch_ex", "mh_batch_plan_ex",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -121,6 +123,13 @@ class mh_batch_item(ctypes.Structure):
                 ("slots", ctypes.c_uint32)]
 
 
+class mh_batch_piece(ctypes.Structure):
+    _fields_ = [("req", ctypes.c_uint64), ("first", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("kind", ctypes.c_int32), ("pass", ctypes.c_int32), ("slot", ctypes.c_uint32),
+                ("slots", ctypes.c_uint32), ("word", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("lo_digits", ctypes.c_int32), ("launch", ctypes.c_int32)]
+
+
 class mh_message(ctypes.Structure):
     _fields_ = [("type", ctypes.c_int64), ("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64),
                 ("hash", ctypes.c_uint64), ("nonce", ctypes.c_uint64), ("data_len", ctypes.c_size_t)]
@@ -195,6 +204,10 @@ def _load():
     L.mh_hits_batch_regions.argtypes = [ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hits_region),
                                         ctypes.c_int64]
     L.mh_batch_plan.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_batch_item), ctypes.c_int64]
+    L.mh_search_batch_ex.argtypes = [ctypes.c_int, ctypes.POINTER(mh_request), sz, ctypes.c_uint32,
+                                     ctypes.POINTER(mh_result)]
+    L.mh_batch_plan_ex.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.c_uint32, ctypes.POINTER(mh_batch_piece),
+                                   ctypes.c_int64]
     L.mh_miner_handle_batch.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz,
                                         ctypes.c_char_p, sz, ctypes.POINTER(sz), intp]
     vp = ctypes.c_void_p
@@ -217,6 +230,7 @@ def _load():
     L.mh_server_pop_write.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_char_p, sz, ctypes.POINTER(sz)]
     L.mh_server_stats.argtypes = [vp, ctypes.POINTER(mh_sched_stats)]
     restype = {"mh_plan": ctypes.c_int64, "mh_multi_plan": ctypes.c_int64, "mh_batch_plan": ctypes.c_int64,
+               "mh_batch_plan_ex": ctypes.c_int64,
                "mh_first_batch_order": ctypes.c_int64, "mh_hits_batch_regions": ctypes.c_int64,
                "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,

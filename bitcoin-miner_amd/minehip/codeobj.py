@@ -42,6 +42,14 @@ def hits_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def batch_code_object():
+    """The embedded code object of the batch kernels (mh_search_batch_ex): batch_fast<J, MODE>,
+    fast_search.hip built with -DMH_BATCH (mh_batch_co_begin .. mh_batch_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def unpack_msgpack(b):
     """Decode one MessagePack object (the subset AMDGPU metadata uses: maps, arrays, strings,
     binary, integers, floats, booleans, nil).  No dependency on the msgpack package."""
@@ -152,3 +160,8 @@ def first_kernel_resources():
 def hits_kernel_resources():
     """The same of the embedded hits_scan<J, MODE> kernels."""
     return fast_kernel_resources(hits_code_object(), r"_ZN2mh9hits_scanILi(\d+)ELi(\d+)E")
+
+
+def batch_kernel_resources(co=None):
+    """The same of the embedded batch_fast<J, MODE> kernels (or of those of code object `co`)."""
+    return fast_kernel_resources(batch_code_object() if co is None else co, r"_ZN2mh10batch_fastILi(\d+)ELi(\d+)E")

@@ -130,6 +130,24 @@ typedef struct mh_result {
  * code and leaves out undefined.  One device only. */
 int mh_search_batch(int dev, const mh_request *reqs, size_t n, mh_result *out);
 
+/* mh_search_batch with flags.  flags == 0 is exactly mh_search_batch; an unknown flag bit returns
+ * MH_EINVAL.  MH_BATCH_FUSE_FAST also fuses the requests whose plan holds fast pieces: the pieces
+ * of one layout <J, MODE> of a pass run as one launch of the batch_fast<J, MODE> kernel (the
+ * product's per-nonce loop, one workgroup per 256-run chunk of a table of pieces) beside the pass's
+ * batch_scan launch, into the same per-request slot segments, so a pass is still one copy of
+ * tables, its launches, one segmented merge and one copy-back, and the call one host synchronise.
+ * A request is fused when its tiles and chunks fit one pass (2^18 slots; MINEHIP_BATCH_SLOTS), its
+ * entries and its fast pieces (at most 1,024) one pass's tables, and it has at most
+ * MH_BATCH_FAST_MAX_NONCES nonces; anything else is a fallback as in mh_search_batch.  Every
+ * request keeps the pieces and lanes of its own mh_search plan (mh_batch_plan_ex shows the plan;
+ * DESIGN.md section 3 has the measurements behind the cap and the lane rule).
+ * out[i] is what mh_search returns for request i, bit for bit, whatever the batch holds, the lanes
+ * chosen, the passes, the launch order or the fused / fallback split.  Errors are
+ * mh_search_batch's.  Additive in ABI 5 (no existing struct or function changes). */
+#define MH_BATCH_FUSE_FAST 1u
+#define MH_BATCH_FAST_MAX_NONCES 1000000000ull
+int mh_search_batch_ex(int dev, const mh_request *reqs, size_t n, uint32_t flags, mh_result *out);
+
 /* ---- first-hit search: the smallest nonce whose hash meets a target ------ */
 
 typedef struct mh_first {
@@ -403,6 +421,27 @@ typedef struct mh_batch_item {
  * are more than cap (the first cap written, as mh_plan), or the MH_E* of the first request
  * mh_search would refuse.  n == 0 returns 0. */
 int64_t mh_batch_plan(const mh_request *reqs, size_t n, mh_batch_item *out, int64_t cap);
+
+/* One piece of a fused request of mh_search_batch_ex's plan, or one fallback request. */
+typedef struct mh_batch_piece {
+    uint64_t req;          /* index into reqs */
+    uint64_t first, count; /* the piece's nonces; fallback: the request's (count mod 2^64) */
+    int32_t kind;          /* 0 fused generic entry, 1 fallback, 2 fused fast piece */
+    int32_t pass;          /* fused: its pass, from 0; fallback: -1 */
+    uint32_t slot, slots;  /* fused: first partial slot within the pass, and its tiles (kind 0, as
+                              mh_batch_item) or 256-run chunks (kind 2); fallback: 0, 0 */
+    int32_t word, mode, lo_digits; /* kind 2: J, MODE and L, as mh_piece; else 0 */
+    int32_t launch;        /* kind 2: index of its batch_fast launch within the pass (one launch per
+                              layout, pieces ordered by L descending, then request order); else -1 */
+} mh_batch_piece;
+
+/* Host only: how mh_search_batch_ex(flags) would run reqs[0..n): one piece per entry and per fast
+ * piece of a fused request, in nonce order, and one (slots = 0) per fallback request, in request
+ * order.  Within a pass the fused requests' slot segments are contiguous, disjoint and in order,
+ * and a request's pieces fill its segment in nonce order.  flags == 0: mh_batch_plan's plan.
+ * Honours every MINEHIP_* planning variable the call honours.  Returns as mh_batch_plan does;
+ * MH_EINVAL for an unknown flag bit. */
+int64_t mh_batch_plan_ex(const mh_request *reqs, size_t n, uint32_t flags, mh_batch_piece *out, int64_t cap);
 
 /* Host only: the dispatch order of pass `pass` of mh_search_first_batch over reqs[0..n) (the plan
  * is mh_batch_plan's; the targets play no part): out[b] is the partial slot of the tile that
