@@ -49,8 +49,9 @@ def split_line(m):
 
 
 # entry label of a fast kernel: fast_search<J, MODE>, first_scan<J, MODE> of the -DMH_FIRST build
-# or hits_scan<J, MODE> of the -DMH_HITS build or batch_fast<J, MODE> of the -DMH_BATCH builds
-KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast)\S*:")
+# or hits_scan<J, MODE> of the -DMH_HITS build or batch_fast<J, MODE> of the -DMH_BATCH builds or
+# batch_first<J, MODE> of the -DMH_BATCH -DMH_FIRST build
+KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first)\S*:")
 
 
 def split(text, k, pattern=None, phase=None):
@@ -144,8 +145,12 @@ def loop_add3(text):
     import os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import loop_mix
+    bodies = loop_mix.kernels(text)
+    # batch_first exits early (a skipped chunk): its loops lie behind the first s_endpgm
+    bodies.update({name: body for name, body in loop_mix.kernels(text, whole=True).items()
+                   if loop_mix.BATCH_FIRST.match(name)})
     return {name: sum(o == "v_add3_u32" for o in loop_mix.per_nonce_loop(body))
-            for name, body in loop_mix.kernels(text).items() if KERNEL.match(name + ":")}
+            for name, body in bodies.items() if KERNEL.match(name + ":")}
 
 
 def phases_like(text, k, like):

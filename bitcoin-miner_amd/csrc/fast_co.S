@@ -7,7 +7,9 @@
    and the hits kernels of mh_search_hits (-DMH_HITS, build/fast_hits.hsaco),
    loaded per device by the first mh_search_hits, and the batch kernels of
    mh_search_batch_ex (-DMH_BATCH, build/fast_batch.hsaco), loaded per device
-   by the first such call that fuses a fast piece. */
+   by the first such call that fuses a fast piece, and the first-hit batch
+   kernels of mh_search_first_batch_ex (-DMH_BATCH -DMH_FIRST,
+   build/fast_batch_first.hsaco), loaded likewise. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -41,4 +43,12 @@ mh_batch_co_begin:
     .globl mh_batch_co_end
 mh_batch_co_end:
     .size mh_batch_co_begin, mh_batch_co_end - mh_batch_co_begin
+    .p2align 12
+    .globl mh_batch_first_co_begin
+    .type mh_batch_first_co_begin, @object
+mh_batch_first_co_begin:
+    .incbin "fast_batch_first.hsaco"
+    .globl mh_batch_first_co_end
+mh_batch_first_co_end:
+    .size mh_batch_first_co_begin, mh_batch_first_co_end - mh_batch_first_co_begin
     .section .note.GNU-stack,"",@progbits

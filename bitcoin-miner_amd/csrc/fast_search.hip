@@ -25,6 +25,9 @@
 // -DMH_BATCH builds batch_fast<J, MODE> (build/fast_batch.hsaco, through the same passes; DESIGN.md
 // §3): the same chunk body, one workgroup per chunk of a table of many requests' pieces, a fourth
 // embedded code object that mh_search_batch_ex loads; likewise (with -DMH_HASH_KEEP: its test variant).
+// -DMH_BATCH -DMH_FIRST builds batch_first<J, MODE> (build/fast_batch_first.hsaco, through the same
+// passes): batch_fast's table and grid around the first-hit chunk body, a fifth
+// embedded code object that mh_search_first_batch_ex loads; likewise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -569,7 +572,79 @@ __device__ __forceinline__ uint32_t claim_chunk(uint32_t* counter) {
     return blk;
 }
 
+#ifdef MH_FIRST
+// (for both first-hit builds: claim_first of first_scan and, with MH_BATCH, batch_first)
+// No nonce of chunk blk is smaller: lane 0's first.  Last-digit layouts: run U's nonces are
+// U * 10^L + q.  Early layouts: nonce(U, g, i) = spread(U) * u_mul + (terms >= 0 of g and i), and
+// spread is strictly increasing in U, so the chunk's smallest U at g = i = 0 bounds every lane's
+// interleaved nonces from below (it is attained, so the bound is exact).
+template <int MODE>
+__device__ __forceinline__ uint64_t chunk_floor(const FastArgs& a, uint32_t blk) {
+    const uint64_t u0 = a.u_start + (uint64_t)blk * kBlockThreads;
+    if constexpr (MODE < (int)kModeOneEarly)
+        return u0 * a.pow10L;
+    else
+        return spread(u0, a.hole, a.hole_w) * a.u_mul;
+}
+#endif
+
 #ifdef MH_BATCH
+#ifdef MH_FIRST
+// ---------------------------------------------------------------------------
+// batch_first<J, MODE>: the fast pieces of many first-hit requests in one launch,
+// for mh_search_first_batch_ex(MH_BATCH_FUSE_FAST)
+// ---------------------------------------------------------------------------
+// batch_fast's static grid and tables (below) around the first-hit chunk body.  Workgroup b runs
+// chunk order[b] of the launch -- the host's dispatch order, a permutation of the launch's chunks --
+// of the item chunk_item[order[b]] names, read through readfirstlane, so the item's arguments are
+// scalar loads (layout.hpp BatchFirstItem: the request's FirstArgs sit where first_scan's kernarg
+// segment holds them, so fast_chunk reaches them through first_args unchanged).  Before any hashing
+// thread 0 reads the request's `first` word once: a chunk all of whose nonces are larger
+// (chunk_floor, attained, so exact) writes the sentinel its slot's merge expects and ends;
+// otherwise its valid nonces count as scanned and the chunk runs to its end, where key 0 lowers
+// the word.  The word only decreases and always holds a qualifying nonce of the request, so the
+// chunk of the smallest one and every chunk holding a smaller nonce run whatever value the read
+// returns: a stale read only skips less (claim_first's argument).  No workgroup waits for another,
+// no counter and no work queue: the grid always drains.
+static_assert(__builtin_offsetof(BatchFirstItem, f) == __builtin_offsetof(FirstKernArgs, f) &&
+                  __builtin_offsetof(BatchFirstItem, args) == 0,
+              "first_args finds an item's FirstArgs where first_scan's kernarg segment holds them");
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_first(const BatchFirstItem* __restrict__ items,
+                                                                           const uint32_t* __restrict__ chunk_item,
+                                                                           const uint32_t* __restrict__ order,
+                                                                           Partial* __restrict__ partials) {
+    using KItem = __attribute__((address_space(4))) const BatchFirstItem;
+    __shared__ uint32_t s_skip;
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[blockIdx.x]);
+    const uint32_t ii = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk_item[c]);
+    KItem* k = (KItem*)(items + ii);
+    asm volatile("" : "+s"(k));
+    const uint32_t blk = c - k->chunk0, slot0 = k->slot0;
+    if (threadIdx.x == 0) {
+        const FastArgs& a = ((const BatchFirstItem*)k)->args;
+        const FirstArgs& f = ((const BatchFirstItem*)k)->f;
+        const uint64_t seen = __hip_atomic_load(f.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t skip = 0u;
+        if (chunk_floor<MODE>(a, blk) > seen) {
+            uint64_t ones = ~0ull;
+            asm volatile("" : "+v"(ones));  // made here, as claim_first's
+            partials[slot0 + blk] = Partial{ones, ones};
+            skip = 1u;
+        } else {
+            // this chunk will be run: its valid nonces count as scanned
+            const uint32_t left = a.n_runs - blk * (uint32_t)kBlockThreads;  // blk < n_chunks: >= 1
+            const uint32_t lanes = left < (uint32_t)kBlockThreads ? left : (uint32_t)kBlockThreads;
+            atomicAdd(f.scanned, (unsigned long long)lanes * a.n_groups * 10ull);
+        }
+        s_skip = skip;
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(s_skip)) return;  // one value per workgroup: scalar
+    asm volatile("" : "+s"(k));
+    fast_chunk<J, MODE>(((const BatchFirstItem*)k)->args, partials + slot0, blk);
+}
+#else
 // ---------------------------------------------------------------------------
 // batch_fast<J, MODE>: the fast pieces of many requests in one launch, for
 // mh_search_batch_ex(MH_BATCH_FUSE_FAST)
@@ -594,6 +669,7 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_fast(
     asm volatile("" : "+s"(k));
     fast_chunk<J, MODE>(((const BatchFastItem*)k)->args, partials + slot0, b - chunk0);
 }
+#endif
 #else
 #ifndef MH_FIRST
 template <int J, int MODE>
@@ -629,19 +705,6 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void fast_search
 // ---------------------------------------------------------------------------
 // first_scan<J, MODE>: the same chunks, for mh_search_first
 // ---------------------------------------------------------------------------
-// No nonce of chunk blk is smaller: lane 0's first.  Last-digit layouts: run U's nonces are
-// U * 10^L + q.  Early layouts: nonce(U, g, i) = spread(U) * u_mul + (terms >= 0 of g and i), and
-// spread is strictly increasing in U, so the chunk's smallest U at g = i = 0 bounds every lane's
-// interleaved nonces from below (it is attained, so the bound is exact).
-template <int MODE>
-__device__ __forceinline__ uint64_t chunk_floor(const FastArgs& a, uint32_t blk) {
-    const uint64_t u0 = a.u_start + (uint64_t)blk * kBlockThreads;
-    if constexpr (MODE < (int)kModeOneEarly)
-        return u0 * a.pow10L;
-    else
-        return spread(u0, a.hole, a.hole_w) * a.u_mul;
-}
-
 // claim_chunk with one more word per claim: thread 0 reads *f.first, the smallest qualifying
 // nonce any finished chunk of this search has reported (all ones: none), beside the claim; a chunk
 // all of whose nonces are larger is skipped -- thread 0 writes the sentinel its slot's merge
@@ -716,9 +779,15 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void first_scan(
 // older sources runs one workgroup per chunk instead of searching only its first chunks.
 extern "C" {
 #ifdef MH_BATCH
+#ifdef MH_FIRST
+// Marker of the first-hit batch code object instead: its kernels read BatchFirstItems of this size
+// (the library launches batch_first only from a code object that carries it, search_kernels.hip).
+__device__ __attribute__((used)) uint8_t mh_fast_batch_first_items[sizeof(BatchFirstItem)];
+#else
 // Marker of the batch code object instead: its kernels read BatchFastItems of this size (the
 // library launches batch_fast only from a code object that carries it, search_kernels.hip).
 __device__ __attribute__((used)) uint8_t mh_fast_batch_items[sizeof(BatchFastItem)];
+#endif
 #else
 __device__ __attribute__((used)) uint8_t mh_fast_queue_args[sizeof(FastArgs)];
 #endif
@@ -737,9 +806,15 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 // costs less with the digit ending word J innermost than with the last digit
 // in word J + 1 (plan.cpp: nonce_cost(J) < nonce_cost(J + 1)).
 #ifdef MH_BATCH
+#ifdef MH_FIRST
+#define MH_INST(j, m) \
+    template __global__ void batch_first<j, m>(const BatchFirstItem* __restrict__, const uint32_t* __restrict__, \
+                                               const uint32_t* __restrict__, Partial* __restrict__);
+#else
 #define MH_INST(j, m) \
     template __global__ void batch_fast<j, m>(const BatchFastItem* __restrict__, const uint32_t* __restrict__, \
                                               Partial* __restrict__);
+#endif
 #else
 #ifndef MH_FIRST
 #ifdef MH_HITS

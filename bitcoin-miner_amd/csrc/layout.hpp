@@ -218,6 +218,22 @@ struct BatchFirstResult {
     uint64_t hash, nonce, scanned;
 };
 
+// ---- fused fast pieces of a first-hit batch (batch_first<J, MODE> of build/fast_batch_first.hsaco) ----
+// One fast piece of one request of a pass of mh_search_first_batch_ex(MH_BATCH_FUSE_FAST): a
+// BatchFastItem with the request's first-hit parameters where first_scan's kernarg segment holds
+// them -- FirstArgs one pointer behind FastArgs -- so the chunk body reaches them as it does there.
+// f.first and f.scanned are device addresses into the request's BatchFirstWords, filled in by the
+// host once it knows where the pass's tables go.  Workgroup b of the launch runs chunk
+// order[b] - chunk0 of the item chunk_item[order[b]] names and writes partials[slot0 + that chunk].
+struct BatchFirstItem {
+    FastArgs args;
+    Partial* unused;      // null; where first_scan's partials parameter sits
+    FirstArgs f;
+    uint32_t chunk0;      // first chunk of the item in its launch
+    uint32_t slot0;       // first partial slot of the item in its pass
+};
+static_assert(sizeof(BatchFirstItem) % 16 == 0, "items are laid out back to back in the pass's tables");
+
 // ---- batched hits (batch_scan_hits / merge_segments_hits) ----
 // The device words of one request of a pass of mh_search_hits_batch, in a table parallel to the
 // segments, found by a tile through entry_req[entry] as BatchFirstWords are.  Every nonce of the

@@ -18,11 +18,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from valu_rates import valu_rate  # noqa: E402  (the opcode tables of the issue-priority pass)
 
 
-def kernels(text):
-    """{mangled name: assembly body up to its s_endpgm} for every kernel of the file."""
+def kernels(text, whole=False):
+    """{mangled name: assembly body up to its s_endpgm} for every kernel of the file.  whole: up
+    to the function's end label instead -- a kernel with an early exit before its loops (batch_first:
+    a skipped chunk ends the workgroup) has an s_endpgm ahead of them."""
     out = {}
     for m in re.finditer(r"^(_Z\S+):", text, flags=re.M):
-        end = text.find("s_endpgm", m.end())
+        end = text.find(".Lfunc_end" if whole else "s_endpgm", m.end())
         out[m.group(1)] = text[m.end():end]
     return out
 
@@ -60,13 +62,15 @@ FAST = re.compile(r"^_ZN2mh11fast_searchILi(\d+)ELi(\d+)EE")
 FIRST = re.compile(r"^_ZN2mh10first_scanILi(\d+)ELi(\d+)EE")  # the -DMH_FIRST build's kernels (build/fast_first_prio.s)
 HITS = re.compile(r"^_ZN2mh9hits_scanILi(\d+)ELi(\d+)EE")  # the -DMH_HITS build's kernels (build/fast_hits_prio.s)
 BATCH = re.compile(r"^_ZN2mh10batch_fastILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH builds' kernels (build/fast_batch*_prio.s)
+# the -DMH_BATCH -DMH_FIRST build's kernels (build/fast_batch_first_prio.s); with whole=True: they exit early
+BATCH_FIRST = re.compile(r"^_ZN2mh11batch_firstILi(\d+)ELi(\d+)EE")
 
 
-def loop_mix(text, pattern=FAST):
+def loop_mix(text, pattern=FAST, whole=False):
     """{"J,MODE": {"valu": N, "half": H}} of every fast_search kernel's per-nonce loop (pattern:
-    the kernels' mangled names, J and MODE as its groups)."""
+    the kernels' mangled names, J and MODE as its groups; whole: see kernels)."""
     out = {}
-    for name, body in kernels(text).items():
+    for name, body in kernels(text, whole).items():
         m = pattern.match(name)
         if not m:
             continue

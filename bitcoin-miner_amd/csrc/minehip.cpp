@@ -69,6 +69,14 @@ hipError_t launch_batch_scan_first(const BatchEntry* entries, const uint32_t* ti
 hipError_t launch_merge_segments_first(const Partial* partials, const uint32_t* seg, const BatchEntry* entries,
                                        const uint32_t* tile_entry, const BatchFirstWords* words,
                                        BatchFirstResult* results, uint32_t requests, hipStream_t s);
+hipError_t launch_batch_scan_first_slots(const BatchEntry* entries, const uint32_t* tile_entry,
+                                         const uint32_t* entry_req, const uint32_t* order, BatchFirstWords* words,
+                                         Partial* partials, uint32_t tiles, hipStream_t s);
+hipError_t launch_merge_segments_first_ex(const Partial* partials, const uint32_t* seg, const GenArgs* req_gen,
+                                          const BatchFirstWords* words, BatchFirstResult* results, uint32_t requests,
+                                          hipStream_t s);
+hipError_t launch_batch_first(int dev, int J, int mode, const BatchFirstItem* items, const uint32_t* chunk_item,
+                              const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s);
 hipError_t launch_batch_scan_hits(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
                                   BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
                                   hipStream_t s);
@@ -108,6 +116,11 @@ constexpr int kEventPairs = 512;             // profiled launches buffered befor
 constexpr uint32_t kQueueSlots = 4096;       // work-queue counters per search (one per fast launch)
 constexpr size_t kBatchTableBytes = 4u << 20;  // device tables (and their pinned staging) of the batch passes in flight
 constexpr uint32_t kBatchResults = 1u << 16;   // results of the batch passes in flight
+// Tables of the first-hit passes with fused fast pieces in flight, a buffer of their own: such a pass
+// carries two words per slot (its item or entry, and the order), a GenArgs and the words per request
+// and 560-byte items, at most 8 * 2^18 + 8,192 * 136 + 4,096 * (128 + 24 + 4) + 1,024 * 560 + 8,192 * 4
+// = ~4.3 MiB, more than kBatchTableBytes
+constexpr size_t kFirstBatchFastTableBytes = 5u << 20;
 
 struct Timed {
     hipEvent_t start = nullptr, stop = nullptr;
@@ -147,6 +160,9 @@ struct DevCtx {
     // batched first-hit search (mh_search_first_batch), allocated by the first such call
     mh::BatchFirstResult* d_fres = nullptr;  // one result per request of the passes in flight
     mh::BatchFirstResult* h_fres = nullptr;  // pinned
+    // ... with fused fast pieces (mh_search_first_batch_ex), allocated by the first such call that fuses one
+    uint8_t* d_ftab = nullptr;  // the passes' tables (first_batch_run_pass_ex)
+    uint8_t* h_ftab = nullptr;  // pinned staging of the same bytes
     // first-hit search (mh_search_first), allocated by the first such call
     uint64_t* d_first = nullptr;  // [0] smallest qualifying nonce so far, [1] nonces scanned, [2..4] the result
     uint64_t* h_first = nullptr;  // pinned: hash, nonce, scanned
@@ -1209,6 +1225,168 @@ int first_batch_run_fused(int dev, const mh::BatchRequest* reqs, const mh_first_
     return rc;
 }
 
+// ---- batched first-hit search with fused fast pieces (mh_search_first_batch_ex) ----
+
+int first_batch_fast_init_locked(DevCtx* c) {
+    if (!c->d_ftab) MH_HIP(hipMalloc(&c->d_ftab, kFirstBatchFastTableBytes));
+    if (!c->h_ftab) MH_HIP(hipHostMalloc(&c->h_ftab, kFirstBatchFastTableBytes, hipHostMallocDefault));
+    return MH_OK;
+}
+
+// first_batch_run_pass for a pass that holds fast pieces: one H2D copy of all its tables -- entries,
+// segments, per-tile entry, per-entry request, tile order, the requests' words with their initial
+// values, a GenArgs per request, the fast items (each with its request's target and the device
+// addresses of its request's words), per-chunk item and chunk order -- then, on the one stream,
+// batch_scan_first_slots for the generic entries, one batch_first<J, MODE> launch per layout in the
+// plan's order, merge_segments_first_ex and one D2H copy of {hash, nonce, scanned} per request.
+// *toff: bytes of the d_ftab / h_ftab buffer in use by the passes in flight.  The fast launches
+// count in the fast class of the profile as batch_run_pass_ex counts them, each piece with its
+// planned nonces, skipped chunks included (mh_search_first's rule for its first_scan launches).
+int first_batch_run_pass_ex(DevCtx* c, const mh::BatchRequest* reqs, const mh_first_request* src,
+                            const std::vector<mh::BatchPiece>& pieces, const mh::BatchTables& t,
+                            const mh::BatchFastTables& f, uint32_t slot_cap, bool rank_major, BatchPending* pend,
+                            size_t* toff, mh_first_result* out) {
+    mh::FirstBatchFastTables x;
+    mh::build_first_batch_tables_ex(t, f, rank_major, &x);
+    if (!mh::first_batch_tables_ex_ok(t, f, x, slot_cap)) return fail(MH_EINTERNAL, "internal: bad first-hit batch tables");
+    for (size_t k = 0; k < f.items.size(); ++k) {
+        const mh::BatchPiece& p = pieces[f.piece[k]];
+        if (f.items[k].args.mode >= mh::kModeOneEarly && !early_piece_ok(f.items[k].args, p.J))
+            return fail(MH_EINTERNAL, "internal: bad Early piece (an enumerated digit outside word J)");
+    }
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t ni = f.items.size(), chunks = f.chunk_item.size();
+    const size_t o_seg = align16(ne * sizeof(mh::BatchEntry)), o_tile = o_seg + align16((nreq + 1u) * sizeof(uint32_t));
+    const size_t o_ereq = o_tile + align16(tiles * sizeof(uint32_t)), o_order = o_ereq + align16(ne * sizeof(uint32_t));
+    const size_t o_words = o_order + align16(tiles * sizeof(uint32_t));
+    const size_t o_gen = o_words + align16(nreq * sizeof(mh::BatchFirstWords));
+    const size_t o_item = o_gen + nreq * sizeof(mh::GenArgs), o_chunk = o_item + ni * sizeof(mh::BatchFirstItem);
+    const size_t o_corder = o_chunk + align16(chunks * sizeof(uint32_t));
+    const size_t bytes = o_corder + align16(chunks * sizeof(uint32_t));
+    static_assert(sizeof(mh::GenArgs) % 16 == 0 && sizeof(mh::BatchFirstItem) % 16 == 0, "tables stay 16-byte aligned");
+    if (bytes > kFirstBatchFastTableBytes || nreq > kBatchResults)
+        return fail(MH_EINTERNAL, "internal: batch pass too large");
+    if (*toff + bytes > kFirstBatchFastTableBytes || pend->req_idx.size() + nreq > kBatchResults ||
+        (c->prof && c->used + 1 + (int)f.launches.size() > kEventPairs)) {
+        const int rc = first_batch_drain(c, reqs, src, pend, out);
+        if (rc) return rc;
+        *toff = 0;
+    }
+    uint8_t* h = c->h_ftab + *toff;
+    uint8_t* d = c->d_ftab + *toff;
+    memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+    memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    memcpy(h + o_ereq, x.entry_req.data(), ne * sizeof(uint32_t));
+    memcpy(h + o_order, x.tile_order.data(), tiles * sizeof(uint32_t));
+    mh::BatchFirstWords* hw = (mh::BatchFirstWords*)(h + o_words);
+    mh::BatchFirstWords* dw = (mh::BatchFirstWords*)(d + o_words);
+    mh::GenArgs* hg = (mh::GenArgs*)(h + o_gen);
+    for (size_t r = 0; r < nreq; ++r) {
+        hw[r] = mh::BatchFirstWords{src[reqs[t.req_idx[r]].id].target, ~0ull, 0ull};
+        mh::make_gen_args(reqs[t.req_idx[r]].pre, &hg[r]);
+    }
+    mh::BatchFirstItem* hi = (mh::BatchFirstItem*)(h + o_item);
+    for (size_t k = 0; k < ni; ++k) {
+        const uint32_t r = x.item_req[k];  // < nreq, and the request owns the item's slots (checked above)
+        mh::BatchFirstItem it;
+        memset(&it, 0, sizeof it);
+        it.args = f.items[k].args;
+        it.unused = nullptr;
+        it.f = mh::FirstArgs{hw[r].target, &dw[r].first, &dw[r].scanned};
+        it.chunk0 = f.items[k].chunk0;
+        it.slot0 = f.items[k].slot0;
+        hi[k] = it;
+    }
+    memcpy(h + o_chunk, f.chunk_item.data(), chunks * sizeof(uint32_t));
+    memcpy(h + o_corder, x.chunk_order.data(), chunks * sizeof(uint32_t));
+    MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    if (tiles) {
+        Timed* tm = nullptr;
+        if (c->prof) {  // generic class, as first_batch_run_pass
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 1;
+            tm->var = 0;
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_scan_first_slots((const mh::BatchEntry*)d, (const uint32_t*)(d + o_tile),
+                                                 (const uint32_t*)(d + o_ereq), (const uint32_t*)(d + o_order), dw,
+                                                 c->d_partials, (uint32_t)tiles, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[4] += t.nonces;
+        }
+    }
+    for (const mh::BatchFastLaunch& l : f.launches) {
+        Timed* tm = nullptr;
+        if (c->prof) {
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 0;
+            tm->var = var_index(l.J, l.mode, (int)f.items[l.item0].args.L);
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_first(c->dev, l.J, l.mode, (const mh::BatchFirstItem*)(d + o_item),
+                                      (const uint32_t*)(d + o_chunk) + l.chunk0,
+                                      (const uint32_t*)(d + o_corder) + l.chunk0, c->d_partials, l.chunks, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[0] += 1;
+            c->var[tm->var].launches += 1;
+            for (uint32_t k = l.item0; k < l.item0 + l.items; ++k) {
+                const mh::BatchPiece& p = pieces[f.piece[k]];
+                c->cnt[1] += p.count;
+                c->cnt[3] += p.count * (uint64_t)p.ops;
+                c->cnt[6] += p.count * (uint64_t)p.nslots;
+                VarStat& v = c->var[var_index(p.J, p.mode, p.L)];
+                v.nonces += p.count;
+                v.ops += p.count * (uint64_t)p.ops;
+                v.slots += p.count * (uint64_t)p.nslots;
+            }
+        }
+    }
+    const size_t roff = pend->req_idx.size();
+    MH_HIP(mh::launch_merge_segments_first_ex(c->d_partials, (const uint32_t*)(d + o_seg), (const mh::GenArgs*)(d + o_gen),
+                                              dw, c->d_fres + roff, (uint32_t)nreq, c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_fres + roff, c->d_fres + roff, nreq * sizeof(mh::BatchFirstResult), hipMemcpyDeviceToHost,
+                          c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    *toff += bytes;
+    return MH_OK;
+}
+
+// The fused passes of mh_search_first_batch_ex(MH_BATCH_FUSE_FAST), under the device's lock.
+int first_batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const mh_first_request* src,
+                             const std::vector<mh::BatchPiece>& pieces, const std::vector<mh::FastArgs>& args, int passes,
+                             uint32_t slot_cap, mh_first_result* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (!rc) rc = first_batch_init_locked(c);
+    if (rc) return rc;
+    const bool rank_major = first_batch_rank_major();
+    BatchPending pend;
+    size_t toff_fast = 0;
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    for (int p = 0; p < passes && !rc; ++p) {
+        mh::build_batch_tables_ex(reqs, pieces, args, p, &t, &f);
+        if (f.items.empty()) {  // mh_search_first_batch's own pass (slot0 == tile0 throughout)
+            rc = first_batch_run_pass(c, reqs, src, t, slot_cap, rank_major, &pend, out);
+        } else {
+            rc = first_batch_fast_init_locked(c);
+            if (!rc) rc = first_batch_run_pass_ex(c, reqs, src, pieces, t, f, slot_cap, rank_major, &pend, &toff_fast, out);
+        }
+    }
+    if (!rc) rc = first_batch_drain(c, reqs, src, &pend, out);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
 // ---- batched hits ----
 
 // The per-request checks of mh_search_hits_batch: batch_requests' and the cap.
@@ -1666,6 +1844,47 @@ int mh_search_first_batch(int dev, const mh_first_request* reqs, size_t n, mh_fi
     return MH_OK;
 }
 
+int mh_search_first_batch_ex(int dev, const mh_first_request* reqs, size_t n, uint32_t flags, mh_first_result* out) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (!(flags & MH_BATCH_FUSE_FAST)) return mh_search_first_batch(dev, reqs, n, out);
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+#ifdef MH_DEV_HOOKS
+    // as mh_search_first_batch: the first-hit kernels have no variants of these hooks
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_first_batch_ex does not support ") + hook);
+#endif
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    batch_requests(reqs, n, &status, &valid);
+    for (size_t i = 0; i < n; ++i) out[i] = mh_first_result{status[i], 0, 0, 0, 0};
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(valid.data(), valid.size(), plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(),
+                      &pieces, &args);
+    int passes = 0;
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
+    if (passes) {
+        const int rc = first_batch_run_fused_ex(dev, valid.data(), reqs, pieces, args, passes, slot_cap, out);
+        if (rc) return rc;
+    }
+    for (const mh::BatchPiece& p : pieces) {  // the fallbacks, after the fused passes
+        if (p.kind != 1) continue;
+        const mh::BatchRequest& r = valid[p.idx];
+        mh_first f;
+        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, &f);
+        if (rc) return rc;
+        put_first_result(&out[r.id], f.hash, f.nonce, f.scanned, reqs[r.id].target);
+    }
+    return MH_OK;
+}
+
 int64_t mh_first_batch_order(const mh_request* reqs, size_t n, int32_t pass, uint32_t* out, int64_t cap) {
     g_err.clear();
     if (!reqs && n > 0) return fail(MH_EINVAL, "NULL array");
@@ -1694,6 +1913,49 @@ int64_t mh_first_batch_order(const mh_request* reqs, size_t n, int32_t pass, uin
     for (const uint32_t s : ft.order) {
         if (k >= cap) return cap + 1;  // cap + 1 signals truncation
         if (out) out[k] = s;
+        ++k;
+    }
+    return k;
+}
+
+int64_t mh_first_batch_order_ex(const mh_request* reqs, size_t n, uint32_t flags, int32_t pass, int32_t launch,
+                                uint32_t* out, int64_t cap) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (!(flags & MH_BATCH_FUSE_FAST)) {
+        if (launch != -1) return fail(MH_EINVAL, "no such launch");
+        return mh_first_batch_order(reqs, n, pass, out, cap);
+    }
+    if (!reqs && n > 0) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> all;
+    batch_requests(reqs, n, &status, &all);
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])  // the first request mh_search would refuse, as mh_batch_plan
+            return fail(status[i], status[i] == MH_ERANGE ? "lower > upper"
+                                   : status[i] == MH_ETOOLONG ? "message longer than MH_MAX_MSG_LEN" : "msg is NULL");
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(all.data(), n, plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(), &pieces, &args);
+    int passes = 0;
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
+    if (pass < 0 || pass >= passes) return fail(MH_EINVAL, "no such pass");
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    mh::build_batch_tables_ex(all.data(), pieces, args, pass, &t, &f);
+    if (launch < -1 || launch >= (int32_t)f.launches.size()) return fail(MH_EINVAL, "no such launch");
+    mh::FirstBatchFastTables x;
+    mh::build_first_batch_tables_ex(t, f, first_batch_rank_major(), &x);
+    if (!mh::first_batch_tables_ex_ok(t, f, x, slot_cap)) return fail(MH_EINTERNAL, "internal: bad first-hit batch tables");
+    const uint32_t* ord = launch < 0 ? x.tile_order.data() : x.chunk_order.data() + f.launches[(size_t)launch].chunk0;
+    const size_t cnt = launch < 0 ? x.tile_order.size() : f.launches[(size_t)launch].chunks;
+    int64_t k = 0;
+    for (size_t b = 0; b < cnt; ++b) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = mh::first_batch_order_slot(t, f, launch, ord[b]);
         ++k;
     }
     return k;

@@ -992,6 +992,138 @@ bool first_batch_tables_ok(const BatchTables& t, const FirstBatchTables& f) {
     return true;  // tiles distinct values below tiles: a permutation
 }
 
+// ---- batched first-hit search with fused fast pieces ----
+
+namespace {
+// n distinct values below n: a permutation of 0 .. n - 1
+bool is_permutation(const uint32_t* p, size_t n) {
+    std::vector<bool> seen(n, false);
+    for (size_t i = 0; i < n; ++i) {
+        if (p[i] >= n || seen[p[i]]) return false;
+        seen[p[i]] = true;
+    }
+    return true;
+}
+// the request whose segment holds `slot` (the segments are contiguous and non-empty)
+uint32_t slot_request(const BatchTables& t, uint32_t slot) {
+    const size_t nreq = t.req_idx.size();
+    size_t lo = 0, hi = nreq;  // seg[lo] <= slot < seg[hi]
+    while (lo + 1 < hi) {
+        const size_t mid = (lo + hi) / 2;
+        (t.seg[mid] <= slot ? lo : hi) = mid;
+    }
+    return (uint32_t)lo;
+}
+// x zero-extended by w decimal digits at digit index k (fast_search.hip spread)
+uint64_t spread_host(uint64_t x, uint32_t k, uint32_t w) {
+    if (k >= 20u) return x;
+    uint64_t lo = 0, p = 1;
+    for (uint32_t j = 0; j < k; ++j) {
+        lo += (x % 10u) * p;
+        p *= 10u;
+        x /= 10u;
+    }
+    for (uint32_t j = 0; j < w; ++j) p *= 10u;
+    return x * p + lo;
+}
+}  // namespace
+
+uint64_t chunk_floor_host(const FastArgs& a, uint32_t blk) {
+    const uint64_t u0 = a.u_start + (uint64_t)blk * kBlockThreads;
+    return a.mode < kModeOneEarly ? u0 * a.pow10L : spread_host(u0, a.hole, a.hole_w) * a.u_mul;
+}
+
+void build_first_batch_tables_ex(const BatchTables& t, const BatchFastTables& f, bool rank_major,
+                                 FirstBatchFastTables* out) {
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    entry_requests(t, &out->entry_req);
+    out->item_req.clear();
+    for (const BatchFastItem& it : f.items) out->item_req.push_back(slot_request(t, it.slot0));
+    out->tile_order.clear();
+    out->tile_order.reserve(tiles);
+    out->chunk_order.clear();
+    out->chunk_order.reserve(f.chunk_item.size());
+    if (!rank_major) {
+        for (size_t i = 0; i < tiles; ++i) out->tile_order.push_back((uint32_t)i);
+        for (const BatchFastLaunch& l : f.launches)
+            for (uint32_t b = 0; b < l.chunks; ++b) out->chunk_order.push_back(b);
+        return;
+    }
+    // generic launch: per request its tiles [first, end) -- entries, and so tiles, are in request
+    // and nonce order -- and each round emits one tile per request that still has one
+    {
+        std::vector<uint32_t> first(nreq, 0u), end(nreq, 0u);
+        std::vector<bool> any(nreq, false);
+        for (size_t ei = 0; ei < t.entries.size(); ++ei) {
+            const uint32_t r = out->entry_req[ei];
+            const uint32_t t0 = t.entries[ei].tile0;
+            const uint32_t t1 = ei + 1 < t.entries.size() ? t.entries[ei + 1].tile0 : (uint32_t)tiles;
+            if (!any[r]) first[r] = t0;
+            any[r] = true;
+            end[r] = t1;
+        }
+        std::vector<uint32_t> active;
+        for (size_t r = 0; r < nreq; ++r)
+            if (any[r] && first[r] < end[r]) active.push_back((uint32_t)r);
+        for (uint32_t rank = 0; !active.empty(); ++rank) {
+            size_t keep = 0;
+            for (const uint32_t q : active) {
+                out->tile_order.push_back(first[q] + rank);
+                if (first[q] + rank + 1u < end[q]) active[keep++] = q;
+            }
+            active.resize(keep);
+        }
+    }
+    // batch_first launches: each round emits one chunk per item that still has one
+    for (const BatchFastLaunch& l : f.launches) {
+        std::vector<uint32_t> active;
+        for (uint32_t k = l.item0; k < l.item0 + l.items; ++k)
+            if (f.items[k].args.n_chunks) active.push_back(k);
+        for (uint32_t rank = 0; !active.empty(); ++rank) {
+            size_t keep = 0;
+            for (const uint32_t k : active) {
+                out->chunk_order.push_back(f.items[k].chunk0 + rank);
+                if (rank + 1u < f.items[k].args.n_chunks) active[keep++] = k;
+            }
+            active.resize(keep);
+        }
+    }
+}
+
+bool first_batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, const FirstBatchFastTables& x,
+                              uint32_t slot_cap) {
+    if (!batch_tables_ex_ok(t, f, slot_cap)) return false;
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    // every entry's request owns all of the entry's slots
+    if (!entry_requests_ok(t, x.entry_req)) return false;
+    for (size_t ei = 0; ei < t.entries.size(); ++ei) {
+        const BatchEntry& e = t.entries[ei];
+        if ((uint64_t)e.slot0 + batch_tiles(e.g.first, e.g.count) > t.seg[x.entry_req[ei] + 1u]) return false;
+    }
+    // and every item's request all of the item's
+    if (x.item_req.size() != f.items.size()) return false;
+    for (size_t k = 0; k < f.items.size(); ++k) {
+        const uint32_t r = x.item_req[k];
+        const BatchFastItem& it = f.items[k];
+        if (r >= nreq || it.slot0 < t.seg[r] || (uint64_t)it.slot0 + it.args.n_chunks > t.seg[r + 1]) return false;
+    }
+    if (x.tile_order.size() != tiles || !is_permutation(x.tile_order.data(), tiles)) return false;
+    if (x.chunk_order.size() != f.chunk_item.size()) return false;
+    for (const BatchFastLaunch& l : f.launches)  // l.chunk0 + l.chunks <= chunk_item.size() (batch_tables_ex_ok)
+        if (!is_permutation(x.chunk_order.data() + l.chunk0, l.chunks)) return false;
+    return true;
+}
+
+uint32_t first_batch_order_slot(const BatchTables& t, const BatchFastTables& f, int launch, uint32_t v) {
+    if (launch < 0) {
+        const BatchEntry& e = t.entries[t.tile_entry[v]];
+        return e.slot0 + (v - e.tile0);
+    }
+    const BatchFastLaunch& l = f.launches[(size_t)launch];
+    const BatchFastItem& it = f.items[f.chunk_item[l.chunk0 + v]];
+    return it.slot0 + (v - it.chunk0);
+}
+
 // ---- batched hits ----
 
 namespace {

@@ -274,6 +274,37 @@ void build_first_batch_tables(const BatchTables& t, bool rank_major, FirstBatchT
 // segment holds the entry's slots, and order is a permutation of the pass's tiles.
 bool first_batch_tables_ok(const BatchTables& t, const FirstBatchTables& f);
 
+// ---- batched first-hit search with fused fast pieces (mh_search_first_batch_ex) ----
+// The plan is plan_batch_ex's and the tables build_batch_tables_ex's (the targets play no part in
+// either); these are the tables batch_scan_first_slots and batch_first<J, MODE> read beside them.
+struct FirstBatchFastTables {
+    std::vector<uint32_t> entry_req;    // per entry: its request of the pass (index into seg / req_idx)
+    std::vector<uint32_t> item_req;     // per fast item: likewise
+    std::vector<uint32_t> tile_order;   // per workgroup of the generic launch: the tile it runs
+    std::vector<uint32_t> chunk_order;  // per launch (laid out as chunk_item), per workgroup: the chunk of the launch it runs
+};
+// rank_major: the generic launch runs tile 0 of every request that has one, in request order, then
+// tile 1 of every request that has one, and so on (a request's tiles counted across its entries in
+// nonce order); a batch_first launch runs chunk 0 of every item in item order, then chunk 1 of
+// every item that has one, and so on.  Otherwise both are the identity.
+void build_first_batch_tables_ex(const BatchTables& t, const BatchFastTables& f, bool rank_major,
+                                 FirstBatchFastTables* out);
+
+// Checked before every pass: batch_tables_ex_ok(t, f, slot_cap); every entry's and every item's
+// request is the one whose segment holds all of that entry's or item's slots; tile_order is a
+// permutation of the pass's tiles and every launch's part of chunk_order one of that launch's chunks.
+bool first_batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, const FirstBatchFastTables& x,
+                              uint32_t slot_cap);
+
+// The partial slot a workgroup's tile (launch < 0) or chunk of launch `launch` writes, for the
+// order tables as slots (mh_first_batch_order_ex); the tables have passed the check above.
+uint32_t first_batch_order_slot(const BatchTables& t, const BatchFastTables& f, int launch, uint32_t v);
+
+// Host form of the kernels' chunk_floor (fast_search.hip): no nonce of chunk blk of the piece is
+// smaller, and lane 0's first nonce attains it.  Last-digit layouts: (u_start + 256 blk) * 10^L;
+// Early layouts: spread(u_start + 256 blk, hole, hole_w) * u_mul.
+uint64_t chunk_floor_host(const FastArgs& a, uint32_t blk);
+
 // ---- batched hits (mh_search_hits_batch / mh_hits_batch_regions) ----
 // The tables batch_scan_hits reads beside a pass's BatchTables (the plan depends neither on the
 // targets nor on the caps, so plan_batch and build_batch_tables serve unchanged), and the schedule

@@ -42,6 +42,14 @@
 //                         embedded code object, loaded by the first mh_search_batch_ex that fuses one.
 //   batch_scan_slots      batch_scan writing partials[slot0 + tile - tile0]: the generic entries of
 //                         a pass whose slot segments also hold fast chunks.
+//   batch_first<J, MODE>  (fast_search.hip, -DMH_BATCH -DMH_FIRST) batch_fast's table and grid around
+//                         the first-hit chunk body, chunks dispatched in the host's order and skipped
+//                         above their request's hit; a fifth embedded code object, loaded by the first
+//                         mh_search_first_batch_ex that fuses one.
+//   batch_scan_first_slots  batch_scan_first writing partials[slot0 + tile - tile0], as
+//                         batch_scan_slots relates to batch_scan.
+//   merge_segments_first_ex  merge_segments_first with the message state per request, not per tile:
+//                         a fused request may hold no generic entry.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -68,6 +76,8 @@ extern "C" const unsigned char mh_first_co_begin[];
 extern "C" const unsigned char mh_hits_co_begin[];
 // the same source built with -DMH_BATCH: batch_fast<J, MODE>, the fused fast pieces of mh_search_batch_ex
 extern "C" const unsigned char mh_batch_co_begin[];
+// the same source built with -DMH_BATCH -DMH_FIRST: batch_first<J, MODE>, the fused fast pieces of mh_search_first_batch_ex
+extern "C" const unsigned char mh_batch_first_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -453,12 +463,13 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_slots(const BatchEnt
 // every tile with a smaller nonce, runs whatever value the read returns.  A tile that ran lowers
 // the word if it found a hit and adds its valid nonces to `scanned`.  No workgroup waits for
 // another: the grid always drains.  No test hooks.
-__global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEntry* __restrict__ entries,
-                                                                  const uint32_t* __restrict__ tile_entry,
-                                                                  const uint32_t* __restrict__ entry_req,
-                                                                  const uint32_t* __restrict__ order,
-                                                                  BatchFirstWords* words,
-                                                                  Partial* __restrict__ partials) {
+// SLOTS: the tile writes partials[slot0 + tile - tile0] instead of partials[tile] (batch_scan_first_slots).
+template <bool SLOTS>
+__device__ __forceinline__ void batch_scan_first_tile(const BatchEntry* __restrict__ entries,
+                                                      const uint32_t* __restrict__ tile_entry,
+                                                      const uint32_t* __restrict__ entry_req,
+                                                      const uint32_t* __restrict__ order, BatchFirstWords* words,
+                                                      Partial* __restrict__ partials) {
     using namespace dev;
     __shared__ uint32_t s_skip;
     const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[blockIdx.x]);
@@ -467,6 +478,7 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEnt
     const BatchEntry& e = entries[ei];
     const GenArgs& a = e.g;
     BatchFirstWords* w = words + ri;
+    const uint32_t slot = SLOTS ? e.slot0 + (tile - e.tile0) : tile;
     const uint64_t first = a.first, lastn = a.first + (a.count - 1u);
     const uint64_t u_first = first / 10u, u_last = lastn / 10u;
     const uint32_t j_first = (uint32_t)(first - u_first * 10u), j_last = (uint32_t)(lastn - u_last * 10u);
@@ -482,7 +494,7 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEnt
         s_skip = n_lo > __hip_atomic_load(&w->first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
     __syncthreads();
     if (s_skip) {  // one value per workgroup
-        if (threadIdx.x == 0) partials[tile] = Partial{~0ull, ~0ull};
+        if (threadIdx.x == 0) partials[slot] = Partial{~0ull, ~0ull};
         return;
     }
     const uint64_t target = w->target;  // never written on the device
@@ -497,10 +509,33 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEnt
     }
     block_min(bh, bn);
     if (threadIdx.x == 0) {
-        partials[tile] = Partial{bh, bn};
+        partials[slot] = Partial{bh, bn};
         if (bh == 0ull) atomicMin(&w->first, (unsigned long long)bn);
         atomicAdd(&w->scanned, (unsigned long long)(n_hi - n_lo + 1u));
     }
+}
+
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_first(const BatchEntry* __restrict__ entries,
+                                                                  const uint32_t* __restrict__ tile_entry,
+                                                                  const uint32_t* __restrict__ entry_req,
+                                                                  const uint32_t* __restrict__ order,
+                                                                  BatchFirstWords* words,
+                                                                  Partial* __restrict__ partials) {
+    batch_scan_first_tile<false>(entries, tile_entry, entry_req, order, words, partials);
+}
+
+// batch_scan_first for a pass of mh_search_first_batch_ex(MH_BATCH_FUSE_FAST) that holds fast
+// pieces: a request's slot segment holds its tiles and its fast chunks in nonce order, so an
+// entry's slots start at slot0, apart from tile0; order is still a permutation of the pass's tiles
+// (the host checks both and that every slot has exactly one writer, plan.cpp first_batch_tables_ex_ok).
+// The words a tile reads and lowers are the ones batch_first's chunks of the same request use.
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_first_slots(const BatchEntry* __restrict__ entries,
+                                                                        const uint32_t* __restrict__ tile_entry,
+                                                                        const uint32_t* __restrict__ entry_req,
+                                                                        const uint32_t* __restrict__ order,
+                                                                        BatchFirstWords* words,
+                                                                        Partial* __restrict__ partials) {
+    batch_scan_first_tile<true>(entries, tile_entry, entry_req, order, words, partials);
 }
 
 // batch_scan for mh_search_hits_batch: batch_scan's static grid and identity tile
@@ -599,6 +634,37 @@ __global__ __launch_bounds__(kBlockThreads) void merge_segments_first(const Part
     }
 }
 
+// merge_segments_first for a pass of mh_search_first_batch_ex that holds fast pieces: seg[r] is a
+// slot, not a tile, and a request whose range is one fast piece has no entry, so the message state
+// of the winner's hash comes from req_gen[r], a GenArgs per request (mid, tail, plen, t).
+__global__ __launch_bounds__(kBlockThreads) void merge_segments_first_ex(const Partial* __restrict__ partials,
+                                                                         const uint32_t* __restrict__ seg,
+                                                                         const GenArgs* __restrict__ req_gen,
+                                                                         const BatchFirstWords* __restrict__ words,
+                                                                         BatchFirstResult* __restrict__ results) {
+    using namespace dev;
+    const uint32_t r = blockIdx.x;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r]);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r + 1]);
+    uint64_t h = ~0ull, n = ~0ull;
+    for (uint32_t i = a + threadIdx.x; i < b; i += kBlockThreads) {
+        const Partial x = partials[i];
+        if (lex_less(x.hash, x.nonce, h, n)) {
+            h = x.hash;
+            n = x.nonce;
+        }
+    }
+    block_min(h, n);
+    if (threadIdx.x == 0) {
+        if (h == 0ull) {  // only a qualifying nonce has key 0 (the sentinel's is all ones)
+            uint32_t h0, h1;
+            hash_generic(req_gen[r], n, h0, h1);
+            h = ((uint64_t)h0 << 32) | h1;
+        }
+        results[r] = BatchFirstResult{h, n, words[r].scanned};
+    }
+}
+
 // merge_segments for mh_search_hits_batch: the same fold, and results[r] = {hash, nonce, the
 // request's cursor}, final since every tile of the pass has run (stream order).  Then the entries
 // the request's region kept, min(cursor, slots) of them, move to packed[]: behind those of the
@@ -677,7 +743,9 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // hits_scan<J, MODE> of the third (":hits"); no hook replaces either
 // or kFastBatch, batch_fast<J, MODE> of the fourth (":batch"; the dev build reads
 // MINEHIP_DEV_BATCH_CODE_OBJECT, a code object file to use instead: build/fast_batch_keep.hsaco)
-enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3 };
+// or kFastBatchFirst, batch_first<J, MODE> of the fifth (":batch_first"; no hook replaces it), whose
+// marker is mh_fast_batch_first_items at sizeof(BatchFirstItem)
+enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4 };
 #ifdef MH_DEV_HOOKS
 std::string batch_module_path() {
     const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
@@ -689,11 +757,13 @@ std::string batch_module_path() { return ":batch"; }
 hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr,
                          FastVariant variant = kFastProduct) {
     const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
+    const bool bfirst = variant == kFastBatchFirst;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
-    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : (co && *co) ? co : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path()
+                             : bfirst ? ":batch_first" : (co && *co) ? co : "";
 #else
-    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : bfirst ? ":batch_first" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
@@ -702,6 +772,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         const hipError_t e = first          ? hipModuleLoadData(&m, mh_first_co_begin)
                              : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
                              : path == ":batch" ? hipModuleLoadData(&m, mh_batch_co_begin)
+                             : bfirst       ? hipModuleLoadData(&m, mh_batch_first_co_begin)
                              : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
                                             : hipModuleLoad(&m, path.c_str());
         if (e != hipSuccess) {
@@ -714,6 +785,8 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         // (a batch code object: mh_fast_batch_items at sizeof(BatchFastItem), the table layout its kernels read)
         const bool marked = batch ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_items") == hipSuccess &&
                                         gsz == sizeof(BatchFastItem)
+                            : bfirst ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_first_items") == hipSuccess &&
+                                        gsz == sizeof(BatchFirstItem)
                                   : hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_queue_args") == hipSuccess &&
                                         gsz == sizeof(FastArgs);
         (void)hipGetLastError();
@@ -735,7 +808,8 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
     if (fit == g_funcs.end()) {
         char name[96];
         snprintf(name, sizeof name,
-                 first  ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
+                 bfirst ? "_ZN2mh11batch_firstILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
+                 : first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
                  : batch ? "_ZN2mh10batch_fastILi%dELi%dEEEvPKNS_13BatchFastItemEPKjPNS_7PartialE"
                         : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
@@ -967,6 +1041,23 @@ hipError_t launch_batch_fast(int dev, int J, int mode, const BatchFastItem* item
     return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
 }
 
+// One launch of batch_first<J, mode> of the first-hit batch code object (loaded on dev, the current
+// device, by the first call): one workgroup per chunk, workgroup b running chunk order[b] of the
+// launch, chunk_item[c] the item of chunk c (the caller has checked the tables and the order,
+// minehip.cpp first_batch_run_pass_ex).  A code object without the table marker at this library's
+// sizeof(BatchFirstItem) is refused.
+hipError_t launch_batch_first(int dev, int J, int mode, const BatchFirstItem* items, const uint32_t* chunk_item,
+                              const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s) {
+    if (!fast_variant_exists(J, mode) || chunks == 0 || chunks > kMaxBlocksPerLaunch) return hipErrorInvalidValue;
+    hipFunction_t fn;
+    bool marked = false;
+    const hipError_t e = fast_function(dev, J, mode, &fn, &marked, kFastBatchFirst);
+    if (e != hipSuccess) return e;
+    if (!marked) return hipErrorInvalidImage;
+    void* params[] = {&items, &chunk_item, &order, &partials};
+    return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+
 #ifdef MH_DEV_HOOKS
 // The hooks of the batch code object in use on dev (the current device; loaded if need be): whether
 // its kernels mask hashes by FastArgs::pad_ (*keep_ok), and x made its hash-XOR constant if it has
@@ -1015,6 +1106,24 @@ hipError_t launch_merge_segments_first(const Partial* partials, const uint32_t* 
                                        BatchFirstResult* results, uint32_t requests, hipStream_t s) {
     hipLaunchKernelGGL(merge_segments_first, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, entries,
                        tile_entry, words, results);
+    return hipGetLastError();
+}
+
+// The generic side of a first-hit pass that also holds fast pieces: batch_scan_first_slots and
+// merge_segments_first_ex.
+hipError_t launch_batch_scan_first_slots(const BatchEntry* entries, const uint32_t* tile_entry,
+                                         const uint32_t* entry_req, const uint32_t* order, BatchFirstWords* words,
+                                         Partial* partials, uint32_t tiles, hipStream_t s) {
+    hipLaunchKernelGGL(batch_scan_first_slots, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req,
+                       order, words, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_segments_first_ex(const Partial* partials, const uint32_t* seg, const GenArgs* req_gen,
+                                          const BatchFirstWords* words, BatchFirstResult* results, uint32_t requests,
+                                          hipStream_t s) {
+    hipLaunchKernelGGL(merge_segments_first_ex, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, req_gen, words,
+                       results);
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@ tests read like the reference (line numbers into the reference repo):
                              every nonce whose hash is <= target, and how many there are
   search_first_batch(requests)
                              many small first-hit searches fused into one GPU pass
+                             (fuse_fast=True: the fast pieces of larger ones too)
   miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
@@ -183,10 +184,12 @@ def batch_plan_ex(requests, fuse_fast=True, cap=1 << 16, flags=None):
     return [{f: getattr(buf[i], f) for f, _ in mh_batch_piece._fields_} for i in range(k)]
 
 
-def search_first_batch(requests, dev=0, errors="raise"):
+def search_first_batch(requests, dev=0, errors="raise", fuse_fast=False):
     """[(found, hash, nonce, scanned), ...] of many (msg, lower, upper, target) requests: found,
     hash and nonce exactly what search_first() gives for each, with the small ones fused into one
-    GPU pass (mh_search_first_batch).  Per-request failures as search_batch: raised with the
+    GPU pass (mh_search_first_batch).  fuse_fast=True also fuses the fast pieces of the larger
+    requests, up to MH_BATCH_FAST_MAX_NONCES nonces each (mh_search_first_batch_ex with
+    MH_BATCH_FUSE_FAST).  Per-request failures as search_batch: raised with the
     request's index, or with errors="return" left in place in the list."""
     if errors not in ("raise", "return"):
         raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
@@ -205,7 +208,10 @@ def search_first_batch(requests, dev=0, errors="raise"):
         keep.append(m)
         arr[i].msg, arr[i].len, arr[i].lower, arr[i].upper, arr[i].target = m, len(m), lower, upper, target
     out = (mh_first_result * max(1, len(requests)))()
-    _check(lib.mh_search_first_batch(dev, arr, len(requests), out))
+    if fuse_fast:
+        _check(lib.mh_search_first_batch_ex(dev, arr, len(requests), MH_BATCH_FUSE_FAST, out))
+    else:
+        _check(lib.mh_search_first_batch(dev, arr, len(requests), out))
     res = []
     for i in range(len(requests)):
         if out[i].status == MH_OK:
@@ -219,14 +225,21 @@ def search_first_batch(requests, dev=0, errors="raise"):
     return res
 
 
-def first_batch_order(requests, pass_=0, cap=1 << 18):
+def first_batch_order(requests, pass_=0, cap=1 << 18, fuse_fast=False, launch=-1, flags=None):
     """Host-only: the dispatch order of pass `pass_` of search_first_batch over (msg, lower, upper)
     requests (a target, if given, is ignored): entry b is the partial slot of the tile that
-    workgroup b runs (mh_first_batch_order)."""
+    workgroup b runs (mh_first_batch_order).  With fuse_fast=True the pass is one of
+    search_first_batch(fuse_fast=True): launch=-1 is its generic launch, launch >= 0 that
+    batch_first launch, entry b the partial slot of the chunk that workgroup b runs
+    (mh_first_batch_order_ex; `flags` overrides the flag word)."""
     requests = [tuple(r)[:3] for r in requests]
     arr, keep = _requests(requests)
     buf = (ctypes.c_uint32 * cap)()
-    k = lib.mh_first_batch_order(arr, len(requests), pass_, buf, cap)
+    if fuse_fast or launch != -1 or flags is not None:
+        k = lib.mh_first_batch_order_ex(arr, len(requests), (MH_BATCH_FUSE_FAST if fuse_fast else 0) if flags is None
+                                        else flags, pass_, launch, buf, cap)
+    else:
+        k = lib.mh_first_batch_order(arr, len(requests), pass_, buf, cap)
     if k < 0:
         _check(k)
     if k > cap:

@@ -50,6 +50,15 @@ def batch_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def batch_first_code_object():
+    """The embedded code object of the first-hit batch kernels (mh_search_first_batch_ex):
+    batch_first<J, MODE>, fast_search.hip built with -DMH_BATCH -DMH_FIRST
+    (mh_batch_first_co_begin .. mh_batch_first_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_first_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_first_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def unpack_msgpack(b):
     """Decode one MessagePack object (the subset AMDGPU metadata uses: maps, arrays, strings,
     binary, integers, floats, booleans, nil).  No dependency on the msgpack package."""
@@ -165,3 +174,9 @@ def hits_kernel_resources():
 def batch_kernel_resources(co=None):
     """The same of the embedded batch_fast<J, MODE> kernels (or of those of code object `co`)."""
     return fast_kernel_resources(batch_code_object() if co is None else co, r"_ZN2mh10batch_fastILi(\d+)ELi(\d+)E")
+
+
+def batch_first_kernel_resources(co=None):
+    """The same of the embedded batch_first<J, MODE> kernels (or of those of code object `co`)."""
+    return fast_kernel_resources(batch_first_code_object() if co is None else co,
+                                 r"_ZN2mh11batch_firstILi(\d+)ELi(\d+)E")

@@ -208,6 +208,28 @@ typedef struct mh_first_result {
  * fast pieces, nothing in the LSP protocol or the miner.  Additive in ABI 5. */
 int mh_search_first_batch(int dev, const mh_first_request *reqs, size_t n, mh_first_result *out);
 
+/* mh_search_first_batch with flags.  flags == 0 is exactly mh_search_first_batch; an unknown flag
+ * bit returns MH_EINVAL.  MH_BATCH_FUSE_FAST (the only flag) also fuses the requests whose plan holds
+ * fast pieces, exactly as mh_search_batch_ex decides it (the plan is mh_batch_plan_ex's: the same
+ * fused / fallback split, passes, slots, launches and cap, MH_BATCH_FAST_MAX_NONCES; the targets
+ * play no part, and every request keeps the lanes of its own mh_search plan).  The fast pieces of
+ * one layout <J, MODE> of a pass run as one launch of the batch_first<J, MODE> kernel -- the
+ * first-hit per-nonce loop of mh_search_first, one workgroup per 256-run chunk of a table of
+ * pieces -- behind the pass's batch_scan_first launch on the same stream and into the same
+ * per-request slot segments and device words.  Before any hashing a chunk reads its request's
+ * smallest reported hit once and is skipped when all its nonces are larger; a chunk that has
+ * started runs to its end.  No workgroup waits for another.  Inside a launch the chunks are
+ * dispatched rank-major -- chunk 0 of every piece, then chunk 1 of every piece that has one, and
+ * so on (mh_first_batch_order_ex) -- unless MINEHIP_FIRST_BATCH_ORDER=request.  A pass is one copy
+ * of tables, its launches, one segmented merge and one copy-back; the call has one host
+ * synchronise; fallbacks run through the mh_search_first path after the fused passes.
+ * Per request, found, hash and nonce are bit for bit mh_search_first's, whatever the batch holds,
+ * the lanes, the passes, the order, the timing or the fused / fallback split; scanned is
+ * upper - lower + 1 when nothing qualifies and nonce - lower + 1 <= scanned <= upper - lower + 1
+ * otherwise.  Errors and per-request statuses are mh_search_first_batch's.  Additive in ABI 5. */
+int mh_search_first_batch_ex(int dev, const mh_first_request *reqs, size_t n, uint32_t flags,
+                             mh_first_result *out);
+
 /* ---- every hit: all nonces of a range whose hash meets a target ---------- */
 
 #define MH_HITS_MAX_CAP (1u << 20) /* most entries one call returns */
@@ -450,6 +472,19 @@ int64_t mh_batch_plan_ex(const mh_request *reqs, size_t n, uint32_t flags, mh_ba
  * cap + 1 when there are more than cap (the first cap written, as mh_plan), the MH_E* of the
  * first request mh_search would refuse, or MH_EINVAL when the plan has no such pass. */
 int64_t mh_first_batch_order(const mh_request *reqs, size_t n, int32_t pass, uint32_t *out, int64_t cap);
+
+/* Host only: the dispatch order of one launch of pass `pass` of mh_search_first_batch_ex(flags)
+ * over reqs[0..n) (the plan is mh_batch_plan_ex's).  launch == -1: the pass's generic launch
+ * (batch_scan_first), out[b] the partial slot of the tile workgroup b runs, a permutation of the
+ * slots of the pass's generic entries; with flags == 0 that is mh_first_batch_order.  launch >= 0:
+ * that batch_first launch of the pass (mh_batch_piece::launch), out[b] the partial slot of the chunk
+ * workgroup b runs, a permutation of the slots of that launch's pieces.  Rank-major unless
+ * MINEHIP_FIRST_BATCH_ORDER=request.  Returns the launch's workgroup count (0 for the generic launch
+ * of a pass without a generic entry), cap + 1 when there are more than cap (the first cap written),
+ * the MH_E* of the first request mh_search would refuse, or MH_EINVAL for an unknown flag bit or a
+ * pass or launch the plan lacks. */
+int64_t mh_first_batch_order_ex(const mh_request *reqs, size_t n, uint32_t flags, int32_t pass, int32_t launch,
+                                uint32_t *out, int64_t cap);
 
 /* One request of mh_search_hits_batch's schedule. */
 typedef struct mh_hits_region {
