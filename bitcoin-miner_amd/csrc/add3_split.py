@@ -50,8 +50,9 @@ def split_line(m):
 
 # entry label of a fast kernel: fast_search<J, MODE>, first_scan<J, MODE> of the -DMH_FIRST build
 # or hits_scan<J, MODE> of the -DMH_HITS build or batch_fast<J, MODE> of the -DMH_BATCH builds or
-# batch_first<J, MODE> of the -DMH_BATCH -DMH_FIRST build
-KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first)\S*:")
+# batch_first<J, MODE> of the -DMH_BATCH -DMH_FIRST build or batch_hits<J, MODE> of the -DMH_BATCH
+# -DMH_HITS build
+KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits)\S*:")
 
 
 def split(text, k, pattern=None, phase=None):

@@ -9,7 +9,9 @@
    mh_search_batch_ex (-DMH_BATCH, build/fast_batch.hsaco), loaded per device
    by the first such call that fuses a fast piece, and the first-hit batch
    kernels of mh_search_first_batch_ex (-DMH_BATCH -DMH_FIRST,
-   build/fast_batch_first.hsaco), loaded likewise. */
+   build/fast_batch_first.hsaco), loaded likewise, and the hits batch kernels
+   of mh_search_hits_batch_ex (-DMH_BATCH -DMH_HITS,
+   build/fast_batch_hits.hsaco), loaded likewise. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -51,4 +53,12 @@ mh_batch_first_co_begin:
     .globl mh_batch_first_co_end
 mh_batch_first_co_end:
     .size mh_batch_first_co_begin, mh_batch_first_co_end - mh_batch_first_co_begin
+    .p2align 12
+    .globl mh_batch_hits_co_begin
+    .type mh_batch_hits_co_begin, @object
+mh_batch_hits_co_begin:
+    .incbin "fast_batch_hits.hsaco"
+    .globl mh_batch_hits_co_end
+mh_batch_hits_co_end:
+    .size mh_batch_hits_co_begin, mh_batch_hits_co_end - mh_batch_hits_co_begin
     .section .note.GNU-stack,"",@progbits

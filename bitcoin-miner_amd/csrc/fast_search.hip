@@ -28,6 +28,9 @@
 // -DMH_BATCH -DMH_FIRST builds batch_first<J, MODE> (build/fast_batch_first.hsaco, through the same
 // passes): batch_fast's table and grid around the first-hit chunk body, a fifth
 // embedded code object that mh_search_first_batch_ex loads; likewise.
+// -DMH_BATCH -DMH_HITS builds batch_hits<J, MODE> (build/fast_batch_hits.hsaco, through the same
+// passes): batch_fast's table and grid around the hits chunk body, a sixth embedded
+// code object that mh_search_hits_batch_ex loads; likewise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -426,10 +429,22 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
             // which admits what the product admits and every possible hit (a hit has H0 <= target >> 32)
             // (a scalar load per nonce through a laundered pointer: kept in an SGPR across the
             // loop, the word costs the TwoEarly layout's loop two VALU instructions)
+#ifdef MH_BATCH
+            // batch_hits: the kernarg segment holds the launch's three table pointers, so the word
+            // comes from the item `a` heads (layout.hpp BatchHitsItem: HitsArgs where HitsKernArgs
+            // has them): still a scalar load per nonce, at the item's address plus a laundered 32-bit
+            // offset (a laundered copy of the 64-bit item pointer is one SGPR pair more than
+            // <13, TwoEarly> has: two v_readlane_b32 in its loop)
+            using KWord = __attribute__((address_space(4))) const uint32_t;
+            uint32_t thi_off = (uint32_t)__builtin_offsetof(HitsKernArgs, h.target) + 4u;
+            asm volatile("" : "+s"(thi_off));
+            const uint32_t hits_thi = *(KWord*)((__attribute__((address_space(4))) const char*)&a + thi_off);
+#else
             using KHits = __attribute__((address_space(4))) const HitsKernArgs;
             KHits* kh = (KHits*)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(kh));
             const uint32_t hits_thi = (uint32_t)(kh->h.target >> 32);
+#endif
             uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= (wbh0 > hits_thi ? wbh0 : hits_thi)) & valid_mask;
 #else
             uint64_t cm = __builtin_amdgcn_ballot_w64(h0 <= wbh0) & valid_mask;  // MH_FIRST: h0 <= lim
@@ -645,6 +660,38 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_first
     fast_chunk<J, MODE>(((const BatchFirstItem*)k)->args, partials + slot0, blk);
 }
 #else
+#ifdef MH_HITS
+// ---------------------------------------------------------------------------
+// batch_hits<J, MODE>: the fast pieces of many hits requests in one launch, for
+// mh_search_hits_batch_ex(MH_BATCH_FUSE_FAST)
+// ---------------------------------------------------------------------------
+// batch_fast's static grid and tables (below) around the hits chunk body: workgroup b runs chunk
+// b - chunk0 of the item chunk_item[b] names, read through readfirstlane, so the item's arguments
+// are scalar loads (layout.hpp BatchHitsItem: the request's HitsArgs sit where hits_scan's kernarg
+// segment holds them, so fast_chunk reaches them through hits_args unchanged; the per-nonce target
+// word comes from the item too, see the chunk body).  No order table, no skipping and no counter:
+// the count needs every nonce, so every chunk runs exactly once.  The appends are hits_scan's --
+// one vector atomic add on the request's cursor per wave step that holds a hit, vector stores by
+// the lead lane, nothing stored at or past the region's end -- into the region the request's
+// generic tiles (batch_scan_hits_slots) append to through the same cursor.  No workgroup waits for
+// another: the grid always drains.
+static_assert(__builtin_offsetof(BatchHitsItem, h) == __builtin_offsetof(HitsKernArgs, h) &&
+                  __builtin_offsetof(BatchHitsItem, args) == 0,
+              "hits_args finds an item's HitsArgs where hits_scan's kernarg segment holds them");
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_hits(const BatchHitsItem* __restrict__ items,
+                                                                          const uint32_t* __restrict__ chunk_item,
+                                                                          Partial* __restrict__ partials) {
+    using KItem = __attribute__((address_space(4))) const BatchHitsItem;
+    const uint32_t b = blockIdx.x;
+    const uint32_t ii = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk_item[b]);
+    KItem* k = (KItem*)(items + ii);
+    asm volatile("" : "+s"(k));
+    const uint32_t chunk0 = k->chunk0, slot0 = k->slot0;
+    asm volatile("" : "+s"(k));
+    fast_chunk<J, MODE>(((const BatchHitsItem*)k)->args, partials + slot0, b - chunk0);
+}
+#else
 // ---------------------------------------------------------------------------
 // batch_fast<J, MODE>: the fast pieces of many requests in one launch, for
 // mh_search_batch_ex(MH_BATCH_FUSE_FAST)
@@ -669,6 +716,7 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_fast(
     asm volatile("" : "+s"(k));
     fast_chunk<J, MODE>(((const BatchFastItem*)k)->args, partials + slot0, b - chunk0);
 }
+#endif  // MH_HITS
 #endif
 #else
 #ifndef MH_FIRST
@@ -784,9 +832,15 @@ extern "C" {
 // (the library launches batch_first only from a code object that carries it, search_kernels.hip).
 __device__ __attribute__((used)) uint8_t mh_fast_batch_first_items[sizeof(BatchFirstItem)];
 #else
+#ifdef MH_HITS
+// Marker of the hits batch code object instead: its kernels read BatchHitsItems of this size (the
+// library launches batch_hits only from a code object that carries it, search_kernels.hip).
+__device__ __attribute__((used)) uint8_t mh_fast_batch_hits_items[sizeof(BatchHitsItem)];
+#else
 // Marker of the batch code object instead: its kernels read BatchFastItems of this size (the
 // library launches batch_fast only from a code object that carries it, search_kernels.hip).
 __device__ __attribute__((used)) uint8_t mh_fast_batch_items[sizeof(BatchFastItem)];
+#endif  // MH_HITS
 #endif
 #else
 __device__ __attribute__((used)) uint8_t mh_fast_queue_args[sizeof(FastArgs)];
@@ -811,9 +865,15 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
     template __global__ void batch_first<j, m>(const BatchFirstItem* __restrict__, const uint32_t* __restrict__, \
                                                const uint32_t* __restrict__, Partial* __restrict__);
 #else
+#ifdef MH_HITS
+#define MH_INST(j, m) \
+    template __global__ void batch_hits<j, m>(const BatchHitsItem* __restrict__, const uint32_t* __restrict__, \
+                                              Partial* __restrict__);
+#else
 #define MH_INST(j, m) \
     template __global__ void batch_fast<j, m>(const BatchFastItem* __restrict__, const uint32_t* __restrict__, \
                                               Partial* __restrict__);
+#endif  // MH_HITS
 #endif
 #else
 #ifndef MH_FIRST

@@ -254,4 +254,23 @@ struct BatchHitsResult {
     uint64_t hash, nonce, count;
 };
 
+// ---- fused fast pieces of a hits batch (batch_hits<J, MODE> of build/fast_batch_hits.hsaco) ----
+// One fast piece of one request of a pass of mh_search_hits_batch_ex(MH_BATCH_FUSE_FAST): a
+// BatchFastItem with the request's hits parameters where hits_scan's kernarg segment holds them --
+// HitsArgs one pointer behind FastArgs -- so the chunk body reaches them as it does there.  The host
+// fills in the pointers once it knows where the pass's tables go: h.cursor is the device address of
+// the request's BatchHitsWords::cursor, h.hits the request's region of the device hit buffer and
+// h.cap the region's slots, so the fast pieces and the generic tiles of one request append through
+// one cursor into one region.  Workgroup b of the launch runs chunk b - chunk0 of the item
+// chunk_item[b] names and writes partials[slot0 + b - chunk0].
+struct BatchHitsItem {
+    FastArgs args;
+    Partial* unused;      // null; where hits_scan's partials parameter sits
+    HitsArgs h;
+    uint32_t chunk0;      // first chunk of the item in its launch
+    uint32_t slot0;       // first partial slot of the item in its pass
+    uint32_t pad_[2];     // 0
+};
+static_assert(sizeof(BatchHitsItem) % 16 == 0, "items are laid out back to back in the pass's tables");
+
 }  // namespace mh

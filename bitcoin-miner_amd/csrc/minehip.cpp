@@ -80,6 +80,11 @@ hipError_t launch_batch_first(int dev, int J, int mode, const BatchFirstItem* it
 hipError_t launch_batch_scan_hits(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
                                   BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
                                   hipStream_t s);
+hipError_t launch_batch_scan_hits_slots(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
+                                        BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
+                                        hipStream_t s);
+hipError_t launch_batch_hits(int dev, int J, int mode, const BatchHitsItem* items, const uint32_t* chunk_item,
+                             Partial* partials, uint32_t chunks, hipStream_t s);
 hipError_t launch_merge_segments_hits(const Partial* partials, const uint32_t* seg, const BatchHitsWords* words,
                                       const Hit* hits, Hit* packed, uint64_t limit, const unsigned long long* base_in,
                                       unsigned long long* base_out, BatchHitsResult* results, uint32_t requests,
@@ -1573,6 +1578,171 @@ int hits_batch_run_fused(int dev, const mh::BatchRequest* reqs, const mh_hits_re
     return rc;
 }
 
+// ---- batched hits with fused fast pieces (mh_search_hits_batch_ex) ----
+
+// hits_batch_run_pass for a pass that holds fast pieces: one H2D copy of all its tables -- entries,
+// segments, per-tile entry, per-entry request, the requests' words with their initial values
+// (cursor = 0), the fast items (each with its request's target, the device address of its request's
+// cursor and its request's region of the device hit buffer) and per-chunk item -- then, on the one
+// stream, batch_scan_hits_slots for the generic entries, one batch_hits<J, MODE> launch per layout
+// in the plan's order, merge_segments_hits (it reads segments and words, so it serves slot segments
+// unchanged) and one D2H copy of {hash, nonce, count} per request.  Windows, regions and drains are
+// hits_batch_run_pass's; the items and the per-chunk table count against the window's table buffer.
+// The fast launches count in the fast class of the profile as batch_run_pass_ex counts them.
+int hits_batch_run_pass_ex(DevCtx* c, const mh::BatchRequest* reqs, const mh_hits_request* src, const uint64_t* caps,
+                           const std::vector<mh::BatchPiece>& pieces, const mh::BatchTables& t,
+                           const mh::BatchFastTables& f, uint32_t slot_cap, const mh::HitsBatchLimits& lim,
+                           HitsBatchPending* pend, mh_hit* hits, mh_hits_result* out, std::vector<size_t>* rebuild,
+                           std::vector<mh::Hit>* stage) {
+    if (!mh::batch_tables_ex_ok(t, f, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+    for (size_t k = 0; k < f.items.size(); ++k) {
+        const mh::BatchPiece& p = pieces[f.piece[k]];
+        if (f.items[k].args.mode >= mh::kModeOneEarly && !early_piece_ok(f.items[k].args, p.J))
+            return fail(MH_EINTERNAL, "internal: bad Early piece (an enumerated digit outside word J)");
+    }
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t ni = f.items.size(), chunks = f.chunk_item.size();
+    const size_t o_seg = align16(ne * sizeof(mh::BatchEntry)), o_tile = o_seg + align16((nreq + 1u) * sizeof(uint32_t));
+    const size_t o_ereq = o_tile + align16(tiles * sizeof(uint32_t)), o_words = o_ereq + align16(ne * sizeof(uint32_t));
+    const size_t o_item = o_words + align16(nreq * sizeof(mh::BatchHitsWords));
+    const size_t o_chunk = o_item + ni * sizeof(mh::BatchHitsItem);
+    const size_t bytes = o_chunk + align16(chunks * sizeof(uint32_t));
+    static_assert(sizeof(mh::BatchHitsItem) % 16 == 0 && sizeof(mh::BatchHitsWords) % 16 == 0, "tables stay 16-byte aligned");
+    if (bytes != mh::hits_batch_table_bytes_ex(ne, nreq, tiles, ni, chunks) || bytes > kBatchTableBytes ||
+        nreq > kBatchResults)
+        return fail(MH_EINTERNAL, "internal: batch pass too large");
+    // the event pool cannot take the pass's launches: a drain of its own
+    if (c->prof && c->used + 1 + (int)f.launches.size() > kEventPairs) {
+        const int rc = hits_batch_drain(c, reqs, src, pend, hits, out, rebuild, stage);
+        if (rc) return rc;
+        mh::hits_batch_drained(&pend->st);
+    }
+    mh::HitsBatchFastTables x;
+    mh::HitsBatchState next = pend->st;
+    const bool drain = mh::plan_hits_batch_pass_ex(t, f, reqs, caps, lim, &next, &x);
+    if (drain) {
+        const int rc = hits_batch_drain(c, reqs, src, pend, hits, out, rebuild, stage);
+        if (rc) return rc;
+    }
+    const uint64_t used_before = drain ? 0u : pend->st.used;
+    const size_t toff = drain ? 0u : pend->st.toff;
+    pend->st = next;
+    if (!mh::hits_batch_tables_ex_ok(t, f, reqs, x, slot_cap, used_before,
+                                     std::min<uint64_t>(lim.window_slots, MH_HITS_MAX_CAP)) ||
+        toff + bytes > kBatchTableBytes || pend->req_idx.size() + nreq > kBatchResults)
+        return fail(MH_EINTERNAL, "internal: bad hits batch tables");
+    uint8_t* h = c->h_btab + toff;
+    uint8_t* d = c->d_btab + toff;
+    memcpy(h, t.entries.data(), ne * sizeof(mh::BatchEntry));
+    memcpy(h + o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    memcpy(h + o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    memcpy(h + o_ereq, x.h.entry_req.data(), ne * sizeof(uint32_t));
+    mh::BatchHitsWords* hw = (mh::BatchHitsWords*)(h + o_words);
+    mh::BatchHitsWords* dw = (mh::BatchHitsWords*)(d + o_words);
+    for (size_t r = 0; r < nreq; ++r)
+        hw[r] = mh::BatchHitsWords{src[reqs[t.req_idx[r]].id].target, 0ull, x.h.region[r].offset, x.h.region[r].slots};
+    mh::BatchHitsItem* hi = (mh::BatchHitsItem*)(h + o_item);
+    for (size_t k = 0; k < ni; ++k) {
+        const uint32_t r = x.item_req[k];  // < nreq, and the request owns the item's slots (checked above)
+        mh::BatchHitsItem it;
+        memset(&it, 0, sizeof it);
+        it.args = f.items[k].args;
+        it.unused = nullptr;
+        // the region lies inside the window, the window inside the device hit buffer (checked above)
+        it.h = mh::HitsArgs{hw[r].target, &dw[r].cursor, c->d_hits + hw[r].offset, hw[r].slots};
+        it.chunk0 = f.items[k].chunk0;
+        it.slot0 = f.items[k].slot0;
+        hi[k] = it;
+    }
+    memcpy(h + o_chunk, f.chunk_item.data(), chunks * sizeof(uint32_t));
+    MH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    if (tiles) {
+        Timed* tm = nullptr;
+        if (c->prof) {  // generic class, as hits_batch_run_pass
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 1;
+            tm->var = 0;
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_scan_hits_slots((const mh::BatchEntry*)d, (const uint32_t*)(d + o_tile),
+                                                (const uint32_t*)(d + o_ereq), dw, c->d_hits, c->d_partials,
+                                                (uint32_t)tiles, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[4] += t.nonces;
+        }
+    }
+    for (const mh::BatchFastLaunch& l : f.launches) {
+        Timed* tm = nullptr;
+        if (c->prof) {
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 0;
+            tm->var = var_index(l.J, l.mode, (int)f.items[l.item0].args.L);
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_hits(c->dev, l.J, l.mode, (const mh::BatchHitsItem*)(d + o_item),
+                                     (const uint32_t*)(d + o_chunk) + l.chunk0, c->d_partials, l.chunks, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[0] += 1;
+            c->var[tm->var].launches += 1;
+            for (uint32_t k = l.item0; k < l.item0 + l.items; ++k) {
+                const mh::BatchPiece& p = pieces[f.piece[k]];
+                c->cnt[1] += p.count;
+                c->cnt[3] += p.count * (uint64_t)p.ops;
+                c->cnt[6] += p.count * (uint64_t)p.nslots;
+                VarStat& v = c->var[var_index(p.J, p.mode, p.L)];
+                v.nonces += p.count;
+                v.ops += p.count * (uint64_t)p.ops;
+                v.slots += p.count * (uint64_t)p.nslots;
+            }
+        }
+    }
+    const size_t roff = pend->req_idx.size();
+    const unsigned long long* base_in = pend->passes ? (const unsigned long long*)c->d_hbase + (pend->passes & 1u) : nullptr;
+    unsigned long long* base_out = (unsigned long long*)c->d_hbase + ((pend->passes + 1u) & 1u);
+    MH_HIP(mh::launch_merge_segments_hits(c->d_partials, (const uint32_t*)(d + o_seg), dw, c->d_hits, c->d_hpacked,
+                                          pend->st.used, base_in, base_out, c->d_hres + roff, (uint32_t)nreq, c->stream));
+    ++pend->passes;
+    MH_HIP(hipMemcpyAsync(c->h_hres + roff, c->d_hres + roff, nreq * sizeof(mh::BatchHitsResult), hipMemcpyDeviceToHost,
+                          c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    pend->region.insert(pend->region.end(), x.h.region.begin(), x.h.region.end());
+    return MH_OK;
+}
+
+// The fused passes of mh_search_hits_batch_ex(MH_BATCH_FUSE_FAST), under the device's lock.
+int hits_batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const mh_hits_request* src, const uint64_t* caps,
+                            const std::vector<mh::BatchPiece>& pieces, const std::vector<mh::FastArgs>& args, int passes,
+                            uint32_t slot_cap, mh_hit* hits, mh_hits_result* out, std::vector<size_t>* rebuild) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (!rc) rc = hits_batch_init_locked(c);
+    if (rc) return rc;
+    const mh::HitsBatchLimits lim = hits_batch_limits();
+    HitsBatchPending pend;
+    std::vector<mh::Hit> stage;
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    for (int p = 0; p < passes && !rc; ++p) {
+        mh::build_batch_tables_ex(reqs, pieces, args, p, &t, &f);
+        // a pass without a fast piece is mh_search_hits_batch's own pass (slot0 == tile0 throughout)
+        rc = f.items.empty()
+                 ? hits_batch_run_pass(c, reqs, src, caps, t, slot_cap, lim, &pend, hits, out, rebuild, &stage)
+                 : hits_batch_run_pass_ex(c, reqs, src, caps, pieces, t, f, slot_cap, lim, &pend, hits, out, rebuild,
+                                          &stage);
+    }
+    if (!rc) rc = hits_batch_drain(c, reqs, src, &pend, hits, out, rebuild, &stage);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2061,6 +2231,149 @@ int64_t mh_hits_batch_regions(const mh_hits_request* reqs, size_t n, mh_hits_reg
         for (size_t r = 0; r < t.req_idx.size(); ++r)
             regions[t.req_idx[r]] = mh_hits_region{all[t.req_idx[r]].id, 0, p, st.window, 0, ht.region[r].offset,
                                                    ht.region[r].slots};
+    }
+    int64_t k = 0;
+    for (const mh_hits_region& g : regions) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = g;
+        ++k;
+    }
+    return k;
+}
+
+int mh_search_hits_batch_ex(int dev, const mh_hits_request* reqs, size_t n, uint32_t flags, mh_hit* hits,
+                            size_t hits_cap, mh_hits_result* out) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (!(flags & MH_BATCH_FUSE_FAST)) return mh_search_hits_batch(dev, reqs, n, hits, hits_cap, out);
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+#ifdef MH_DEV_HOOKS
+    // as mh_search_hits_batch: the hits kernels have no variants of these hooks
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_hits_batch_ex does not support ") + hook);
+#endif
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    std::vector<uint64_t> caps;
+    hits_batch_requests(reqs, n, &status, &valid, &caps);
+    uint64_t total = 0;  // the offsets, as mh_search_hits_batch
+    for (size_t i = 0; i < n; ++i) {
+        out[i] = mh_hits_result{status[i], 0, 0, 0, 0, 0, total};
+        if (reqs[i].cap <= MH_HITS_MAX_CAP) total += reqs[i].cap;
+        if (total > hits_cap) return fail(MH_EINVAL, "the caps add up to more than hits_cap");
+    }
+    if (!hits && total > 0) return fail(MH_EINVAL, "hits is NULL with a cap > 0");
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(valid.data(), valid.size(), plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(),
+                      &pieces, &args);
+    int passes = 0;
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
+    std::vector<size_t> rebuild;  // fused requests whose region dropped entries
+    if (passes) {
+        const int rc = hits_batch_run_fused_ex(dev, valid.data(), reqs, caps.data(), pieces, args, passes, slot_cap, hits,
+                                               out, &rebuild);
+        if (rc) return rc;
+    }
+    // The lists again through the mh_search_hits path.  The fused scan has the exact count, so a
+    // list cut by its cap (stored < count) is rebuilt from a prefix of the range: the `stored`
+    // smallest qualifying nonces of [lower, hi] are those of the whole range once [lower, hi] holds
+    // at least `stored` hits.  The prefix is sized from the observed density with a quarter to
+    // spare and doubled while it holds too few; at hi == upper the count and minimum must agree.
+    for (const size_t idx : rebuild) {
+        const mh::BatchRequest& r = valid[idx];
+        mh_hits_result& o = out[r.id];
+        const double total = (double)(r.upper - r.lower) + 1.0;
+        double want = o.stored < o.count ? 1.25 * total * (double)o.stored / (double)o.count + 1024.0 : total;
+        for (;;) {
+            const uint64_t span = want >= total ? r.upper - r.lower : (uint64_t)want;  // hi - lower
+            const uint64_t hi = span >= r.upper - r.lower ? r.upper : r.lower + span;
+            mh_hits h;
+            const int rc = search_hits_impl(dev, r.pre, r.lower, hi, reqs[r.id].target, hits + o.offset,
+                                            (size_t)reqs[r.id].cap, &h);
+            if (rc) return rc;
+            if (hi == r.upper) {
+                if (h.count != o.count || h.hash != o.hash || h.nonce != o.nonce || h.stored != o.stored)
+                    return fail(MH_EINTERNAL, "internal: a rebuilt hit list disagrees with the fused scan");
+                break;
+            }
+            if (h.count > o.count) return fail(MH_EINTERNAL, "internal: a prefix holds more hits than the fused scan counted");
+            if (h.stored == o.stored) break;  // stored == cap here: the prefix held at least cap hits
+            want *= 2.0;
+        }
+    }
+    for (const mh::BatchPiece& p : pieces) {  // the fallbacks, after the fused passes
+        if (p.kind != 1) continue;
+        const mh::BatchRequest& r = valid[p.idx];
+        mh_hits_result& o = out[r.id];
+        mh_hits h;
+        const int rc = search_hits_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target,
+                                        reqs[r.id].cap ? hits + o.offset : nullptr, (size_t)reqs[r.id].cap, &h);
+        if (rc) return rc;
+        o.count = h.count;
+        o.stored = h.stored;
+        o.hash = h.hash;
+        o.nonce = h.nonce;
+    }
+    return MH_OK;
+}
+
+int64_t mh_hits_batch_regions_ex(const mh_hits_request* reqs, size_t n, uint32_t flags, mh_hits_region* out,
+                                 int64_t cap) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (!(flags & MH_BATCH_FUSE_FAST)) return mh_hits_batch_regions(reqs, n, out, cap);
+    if (n == 0) return 0;
+    if (!reqs) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> all;
+    std::vector<uint64_t> caps;
+    hits_batch_requests(reqs, n, &status, &all, &caps);
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])  // the first request mh_search_hits_batch would refuse
+            return fail(status[i], status[i] == MH_ERANGE     ? "lower > upper"
+                                   : status[i] == MH_ETOOLONG ? "message longer than MH_MAX_MSG_LEN"
+                                   : reqs[i].cap > MH_HITS_MAX_CAP ? "cap is larger than MH_HITS_MAX_CAP"
+                                                                   : "msg is NULL");
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(all.data(), n, plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(), &pieces, &args);
+    int passes = 0;
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
+    std::vector<mh_hits_region> regions(n);
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind == 1) regions[p.idx] = mh_hits_region{p.req, 1, -1, -1, 0, 0, 0};
+    const mh::HitsBatchLimits lim = hits_batch_limits();
+    mh::HitsBatchState st;
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    mh::HitsBatchFastTables x;
+    for (int p = 0; p < passes; ++p) {
+        mh::build_batch_tables_ex(all.data(), pieces, args, p, &t, &f);
+        const uint64_t before = st.used;
+        bool drain;
+        if (f.items.empty()) {  // mh_search_hits_batch's own pass
+            if (!mh::batch_tables_ok(t, slot_cap)) return fail(MH_EINTERNAL, "internal: bad batch tables");
+            drain = mh::plan_hits_batch_pass(t, all.data(), caps.data(), lim, &st, &x.h);
+            if (!mh::hits_batch_tables_ok(t, all.data(), x.h, drain ? 0u : before, lim.window_slots))
+                return fail(MH_EINTERNAL, "internal: bad hits batch tables");
+        } else {
+            drain = mh::plan_hits_batch_pass_ex(t, f, all.data(), caps.data(), lim, &st, &x);
+            if (!mh::hits_batch_tables_ex_ok(t, f, all.data(), x, slot_cap, drain ? 0u : before, lim.window_slots))
+                return fail(MH_EINTERNAL, "internal: bad hits batch tables");
+        }
+        for (size_t r = 0; r < t.req_idx.size(); ++r)
+            regions[t.req_idx[r]] = mh_hits_region{all[t.req_idx[r]].id, 0, p, st.window, 0, x.h.region[r].offset,
+                                                   x.h.region[r].slots};
     }
     int64_t k = 0;
     for (const mh_hits_region& g : regions) {

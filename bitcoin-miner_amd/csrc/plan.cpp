@@ -1147,10 +1147,11 @@ void hits_batch_drained(HitsBatchState* st) {
     ++st->window;
 }
 
-bool plan_hits_batch_pass(const BatchTables& t, const BatchRequest* reqs, const uint64_t* caps,
-                          const HitsBatchLimits& lim, HitsBatchState* st, HitsBatchTables* out) {
+namespace {
+// plan_hits_batch_pass for a pass whose tables take `bytes` of the table buffer
+bool plan_hits_pass(const BatchTables& t, size_t bytes, const BatchRequest* reqs, const uint64_t* caps,
+                    const HitsBatchLimits& lim, HitsBatchState* st, HitsBatchTables* out) {
     const size_t nreq = t.req_idx.size();
-    const size_t bytes = hits_batch_table_bytes(t.entries.size(), nreq, t.tile_entry.size());
     uint64_t want = 0;  // <= kBatchMaxRequests * MH_HITS_MAX_CAP-sized caps: no overflow
     for (size_t r = 0; r < nreq; ++r) want += std::min(caps[t.req_idx[r]], request_size(reqs[t.req_idx[r]]));
     const bool in_flight = st->toff != 0 || st->nres != 0 || st->used != 0;
@@ -1170,6 +1171,13 @@ bool plan_hits_batch_pass(const BatchTables& t, const BatchRequest* reqs, const 
     st->nres += nreq;
     return drain;
 }
+}  // namespace
+
+bool plan_hits_batch_pass(const BatchTables& t, const BatchRequest* reqs, const uint64_t* caps,
+                          const HitsBatchLimits& lim, HitsBatchState* st, HitsBatchTables* out) {
+    return plan_hits_pass(t, hits_batch_table_bytes(t.entries.size(), t.req_idx.size(), t.tile_entry.size()), reqs, caps,
+                          lim, st, out);
+}
 
 bool hits_batch_tables_ok(const BatchTables& t, const BatchRequest* reqs, const HitsBatchTables& h,
                           uint64_t used_before, uint64_t window_slots) {
@@ -1181,6 +1189,46 @@ bool hits_batch_tables_ok(const BatchTables& t, const BatchRequest* reqs, const 
         if (g.offset < next || g.offset > window_slots || g.slots > window_slots - g.offset) return false;
         if (g.slots > request_size(reqs[t.req_idx[r]])) return false;
         next = g.offset + g.slots;
+    }
+    return true;
+}
+
+// ---- batched hits with fused fast pieces ----
+
+size_t hits_batch_table_bytes_ex(size_t entries, size_t requests, size_t tiles, size_t items, size_t chunks) {
+    return hits_batch_table_bytes(entries, requests, tiles) + items * sizeof(BatchHitsItem) +
+           align16(chunks * sizeof(uint32_t));
+}
+
+bool plan_hits_batch_pass_ex(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                             const uint64_t* caps, const HitsBatchLimits& lim, HitsBatchState* st,
+                             HitsBatchFastTables* out) {
+    const size_t bytes = hits_batch_table_bytes_ex(t.entries.size(), t.req_idx.size(), t.tile_entry.size(),
+                                                   f.items.size(), f.chunk_item.size());
+    const bool drain = plan_hits_pass(t, bytes, reqs, caps, lim, st, &out->h);
+    out->item_req.clear();
+    for (const BatchFastItem& it : f.items) out->item_req.push_back(slot_request(t, it.slot0));
+    return drain;
+}
+
+bool hits_batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                             const HitsBatchFastTables& x, uint32_t slot_cap, uint64_t used_before,
+                             uint64_t window_slots) {
+    if (!batch_tables_ex_ok(t, f, slot_cap)) return false;
+    if (!hits_batch_tables_ok(t, reqs, x.h, used_before, window_slots)) return false;
+    const size_t nreq = t.req_idx.size();
+    // every entry's request owns all of the entry's slots
+    for (size_t ei = 0; ei < t.entries.size(); ++ei) {
+        const BatchEntry& e = t.entries[ei];
+        const uint32_t r = x.h.entry_req[ei];  // < nreq (entry_requests_ok)
+        if (e.slot0 < t.seg[r] || (uint64_t)e.slot0 + batch_tiles(e.g.first, e.g.count) > t.seg[r + 1u]) return false;
+    }
+    // and every item's request all of the item's
+    if (x.item_req.size() != f.items.size()) return false;
+    for (size_t k = 0; k < f.items.size(); ++k) {
+        const uint32_t r = x.item_req[k];
+        const BatchFastItem& it = f.items[k];
+        if (r >= nreq || it.slot0 < t.seg[r] || (uint64_t)it.slot0 + it.args.n_chunks > t.seg[r + 1]) return false;
     }
     return true;
 }

@@ -351,4 +351,27 @@ bool plan_hits_batch_pass(const BatchTables& t, const BatchRequest* reqs, const 
 bool hits_batch_tables_ok(const BatchTables& t, const BatchRequest* reqs, const HitsBatchTables& h,
                           uint64_t used_before, uint64_t window_slots);
 
+// ---- batched hits with fused fast pieces (mh_search_hits_batch_ex / mh_hits_batch_regions_ex) ----
+// The plan is plan_batch_ex's and the tables build_batch_tables_ex's (targets and caps play no part
+// in either); these are the tables batch_scan_hits_slots and batch_hits<J, MODE> read beside them.
+// Windows, regions and drains are plan_hits_batch_pass's; the pass's items (BatchHitsItem each) and
+// per-chunk item table count against the table buffer too.
+struct HitsBatchFastTables {
+    HitsBatchTables h;               // per entry its request; per request its region
+    std::vector<uint32_t> item_req;  // per fast item: its request of the pass (index into seg / req_idx)
+};
+// Bytes of such a pass's tables: hits_batch_table_bytes, the items, the per-chunk item table.
+size_t hits_batch_table_bytes_ex(size_t entries, size_t requests, size_t tiles, size_t items, size_t chunks);
+// plan_hits_batch_pass with those bytes, and the items' requests.
+bool plan_hits_batch_pass_ex(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                             const uint64_t* caps, const HitsBatchLimits& lim, HitsBatchState* st,
+                             HitsBatchFastTables* out);
+// Checked before every pass: batch_tables_ex_ok(t, f, slot_cap), hits_batch_tables_ok(t, reqs, x.h,
+// used_before, window_slots), and every entry's and every item's request is the one whose segment
+// holds all of that entry's or item's slots -- so a tile or chunk appends through the cursor, into
+// the region, of the request whose segment its partial goes to.
+bool hits_batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                             const HitsBatchFastTables& x, uint32_t slot_cap, uint64_t used_before,
+                             uint64_t window_slots);
+
 }  // namespace mh

@@ -51,6 +51,14 @@
 //   merge_segments_first_ex  merge_segments_first with the message state per request, not per tile:
 //                         a fused request may hold no generic entry.
 //
+//   batch_hits<J, MODE>   (fast_search.hip, -DMH_BATCH -DMH_HITS) batch_fast's table and grid around
+//                         the hits chunk body, appending through the request's cursor into its
+//                         region; a sixth embedded code object, loaded by the first
+//                         mh_search_hits_batch_ex that fuses one.
+//   batch_scan_hits_slots  batch_scan_hits writing partials[slot0 + tile - tile0], as
+//                         batch_scan_slots relates to batch_scan.  merge_segments_hits serves such
+//                         passes unchanged: it reads the segments and the words, not the entries.
+//
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
 #include <hip/hip_runtime.h>
@@ -78,6 +86,8 @@ extern "C" const unsigned char mh_hits_co_begin[];
 extern "C" const unsigned char mh_batch_co_begin[];
 // the same source built with -DMH_BATCH -DMH_FIRST: batch_first<J, MODE>, the fused fast pieces of mh_search_first_batch_ex
 extern "C" const unsigned char mh_batch_first_co_begin[];
+// the same source built with -DMH_BATCH -DMH_HITS: batch_hits<J, MODE>, the fused fast pieces of mh_search_hits_batch_ex
+extern "C" const unsigned char mh_batch_hits_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -548,11 +558,12 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_first_slots(const Ba
 // buffer and disjoint).  Every nonce of a request belongs to exactly one (tile, lane, digit) and
 // every tile runs exactly once, so the cursor ends as the request's exact count.  No skipping, no
 // waiting, no dependency between workgroups: the grid always drains.  No test hooks.
-__global__ __launch_bounds__(kBlockThreads) void batch_scan_hits(const BatchEntry* __restrict__ entries,
-                                                                 const uint32_t* __restrict__ tile_entry,
-                                                                 const uint32_t* __restrict__ entry_req,
-                                                                 BatchHitsWords* words, Hit* hits,
-                                                                 Partial* __restrict__ partials) {
+// SLOTS: the tile writes partials[slot0 + tile - tile0] instead of partials[tile] (batch_scan_hits_slots).
+template <bool SLOTS>
+__device__ __forceinline__ void batch_scan_hits_tile(const BatchEntry* __restrict__ entries,
+                                                     const uint32_t* __restrict__ tile_entry,
+                                                     const uint32_t* __restrict__ entry_req, BatchHitsWords* words,
+                                                     Hit* hits, Partial* __restrict__ partials) {
     using namespace dev;
     const uint32_t ei = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_entry[blockIdx.x]);
     const uint32_t ri = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry_req[ei]);
@@ -577,7 +588,28 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_hits(const BatchEntr
         }
     }
     block_min(bh, bn);
-    if (threadIdx.x == 0) partials[blockIdx.x] = Partial{bh, bn};
+    if (threadIdx.x == 0) partials[SLOTS ? e.slot0 + (blockIdx.x - e.tile0) : blockIdx.x] = Partial{bh, bn};
+}
+
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_hits(const BatchEntry* __restrict__ entries,
+                                                                 const uint32_t* __restrict__ tile_entry,
+                                                                 const uint32_t* __restrict__ entry_req,
+                                                                 BatchHitsWords* words, Hit* hits,
+                                                                 Partial* __restrict__ partials) {
+    batch_scan_hits_tile<false>(entries, tile_entry, entry_req, words, hits, partials);
+}
+
+// batch_scan_hits for a pass of mh_search_hits_batch_ex(MH_BATCH_FUSE_FAST) that holds fast pieces:
+// a request's slot segment holds its tiles and its fast chunks in nonce order, so an entry's slots
+// start at slot0, apart from tile0 (the host checks that every slot has exactly one writer, plan.cpp
+// hits_batch_tables_ex_ok).  The cursor and the region a tile appends to are the ones batch_hits'
+// chunks of the same request use.
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_hits_slots(const BatchEntry* __restrict__ entries,
+                                                                       const uint32_t* __restrict__ tile_entry,
+                                                                       const uint32_t* __restrict__ entry_req,
+                                                                       BatchHitsWords* words, Hit* hits,
+                                                                       Partial* __restrict__ partials) {
+    batch_scan_hits_tile<true>(entries, tile_entry, entry_req, words, hits, partials);
 }
 
 // One workgroup per request of the pass: results[r] = the lexicographic minimum of
@@ -745,7 +777,9 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // MINEHIP_DEV_BATCH_CODE_OBJECT, a code object file to use instead: build/fast_batch_keep.hsaco)
 // or kFastBatchFirst, batch_first<J, MODE> of the fifth (":batch_first"; no hook replaces it), whose
 // marker is mh_fast_batch_first_items at sizeof(BatchFirstItem)
-enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4 };
+// or kFastBatchHits, batch_hits<J, MODE> of the sixth (":batch_hits"; no hook replaces it), whose
+// marker is mh_fast_batch_hits_items at sizeof(BatchHitsItem)
+enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4, kFastBatchHits = 5 };
 #ifdef MH_DEV_HOOKS
 std::string batch_module_path() {
     const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
@@ -757,13 +791,14 @@ std::string batch_module_path() { return ":batch"; }
 hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr,
                          FastVariant variant = kFastProduct) {
     const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
-    const bool bfirst = variant == kFastBatchFirst;
+    const bool bfirst = variant == kFastBatchFirst, bhits = variant == kFastBatchHits;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
     const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path()
-                             : bfirst ? ":batch_first" : (co && *co) ? co : "";
+                             : bfirst ? ":batch_first" : bhits ? ":batch_hits" : (co && *co) ? co : "";
 #else
-    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : bfirst ? ":batch_first" : "";
+    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : bfirst ? ":batch_first"
+                             : bhits ? ":batch_hits" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
@@ -773,6 +808,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                              : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
                              : path == ":batch" ? hipModuleLoadData(&m, mh_batch_co_begin)
                              : bfirst       ? hipModuleLoadData(&m, mh_batch_first_co_begin)
+                             : bhits        ? hipModuleLoadData(&m, mh_batch_hits_co_begin)
                              : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
                                             : hipModuleLoad(&m, path.c_str());
         if (e != hipSuccess) {
@@ -787,6 +823,8 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                                         gsz == sizeof(BatchFastItem)
                             : bfirst ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_first_items") == hipSuccess &&
                                         gsz == sizeof(BatchFirstItem)
+                            : bhits ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_hits_items") == hipSuccess &&
+                                        gsz == sizeof(BatchHitsItem)
                                   : hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_queue_args") == hipSuccess &&
                                         gsz == sizeof(FastArgs);
         (void)hipGetLastError();
@@ -809,6 +847,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         char name[96];
         snprintf(name, sizeof name,
                  bfirst ? "_ZN2mh11batch_firstILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
+                 : bhits ? "_ZN2mh10batch_hitsILi%dELi%dEEEvPKNS_13BatchHitsItemEPKjPNS_7PartialE"
                  : first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
                  : batch ? "_ZN2mh10batch_fastILi%dELi%dEEEvPKNS_13BatchFastItemEPKjPNS_7PartialE"
@@ -1058,6 +1097,22 @@ hipError_t launch_batch_first(int dev, int J, int mode, const BatchFirstItem* it
     return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
 }
 
+// One launch of batch_hits<J, mode> of the hits batch code object (loaded on dev, the current device,
+// by the first call): one workgroup per chunk, chunk_item[b] the item of chunk b (the caller has
+// checked the tables and the regions, minehip.cpp hits_batch_run_pass_ex).  A code object without
+// the table marker at this library's sizeof(BatchHitsItem) is refused.
+hipError_t launch_batch_hits(int dev, int J, int mode, const BatchHitsItem* items, const uint32_t* chunk_item,
+                             Partial* partials, uint32_t chunks, hipStream_t s) {
+    if (!fast_variant_exists(J, mode) || chunks == 0 || chunks > kMaxBlocksPerLaunch) return hipErrorInvalidValue;
+    hipFunction_t fn;
+    bool marked = false;
+    const hipError_t e = fast_function(dev, J, mode, &fn, &marked, kFastBatchHits);
+    if (e != hipSuccess) return e;
+    if (!marked) return hipErrorInvalidImage;
+    void* params[] = {&items, &chunk_item, &partials};
+    return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+
 #ifdef MH_DEV_HOOKS
 // The hooks of the batch code object in use on dev (the current device; loaded if need be): whether
 // its kernels mask hashes by FastArgs::pad_ (*keep_ok), and x made its hash-XOR constant if it has
@@ -1134,6 +1189,15 @@ hipError_t launch_batch_scan_hits(const BatchEntry* entries, const uint32_t* til
                                   hipStream_t s) {
     hipLaunchKernelGGL(batch_scan_hits, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req, words,
                        hits, partials);
+    return hipGetLastError();
+}
+
+// The generic side of a hits pass that also holds fast pieces: batch_scan_hits_slots.
+hipError_t launch_batch_scan_hits_slots(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
+                                        BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
+                                        hipStream_t s) {
+    hipLaunchKernelGGL(batch_scan_hits_slots, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req,
+                       words, hits, partials);
     return hipGetLastError();
 }
 

@@ -16,6 +16,9 @@ tests read like the reference (line numbers into the reference repo):
   search_first_batch(requests)
                              many small first-hit searches fused into one GPU pass
                              (fuse_fast=True: the fast pieces of larger ones too)
+  search_hits_batch(requests, cap=4096)
+                             every hit of many small requests in one GPU pass
+                             (fuse_fast=True: the fast pieces of larger ones too)
   miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
@@ -270,12 +273,14 @@ def _hits_requests(requests, cap):
     return arr, keep, offsets, total
 
 
-def search_hits_batch(requests, cap=4096, dev=0, errors="raise"):
+def search_hits_batch(requests, cap=4096, dev=0, errors="raise", fuse_fast=False, flags=None):
     """[(count, [(nonce, hash), ...], (min_hash, min_nonce)), ...] of many (msg, lower, upper,
     target) or (msg, lower, upper, target, cap) requests, each exactly what search_hits() gives,
     with the small ones fused into one GPU pass (mh_search_hits_batch); `cap` is the cap of the
-    requests that carry none.  Per-request failures as search_batch: raised with the request's
-    index, or with errors="return" left in place in the list."""
+    requests that carry none.  fuse_fast=True also fuses the fast pieces of the larger requests,
+    up to MH_BATCH_FAST_MAX_NONCES nonces each (mh_search_hits_batch_ex with MH_BATCH_FUSE_FAST;
+    `flags` overrides the flag word).  Per-request failures as search_batch: raised with the
+    request's index, or with errors="return" left in place in the list."""
     if errors not in ("raise", "return"):
         raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
     requests = list(requests)
@@ -283,8 +288,12 @@ def search_hits_batch(requests, cap=4096, dev=0, errors="raise"):
     # not a ctypes array: that would be zero-filled, all sum-of-caps entries of it, on every call
     buf = np.empty((max(1, total), 2), dtype=np.uint64)
     out = (mh_hits_result * max(1, len(requests)))()
-    _check(lib.mh_search_hits_batch(dev, arr, len(requests), buf.ctypes.data_as(ctypes.POINTER(mh_hit)) if total else None,
-                                    total, out))
+    hits = buf.ctypes.data_as(ctypes.POINTER(mh_hit)) if total else None
+    if fuse_fast or flags is not None:
+        _check(lib.mh_search_hits_batch_ex(dev, arr, len(requests), MH_BATCH_FUSE_FAST if flags is None else flags,
+                                           hits, total, out))
+    else:
+        _check(lib.mh_search_hits_batch(dev, arr, len(requests), hits, total, out))
     res = []
     for i in range(len(requests)):
         o = out[i]
@@ -303,14 +312,20 @@ def search_hits_batch(requests, cap=4096, dev=0, errors="raise"):
     return res
 
 
-def hits_batch_regions(requests, cap=4096):
+def hits_batch_regions(requests, cap=4096, fuse_fast=False, flags=None):
     """Host-only: how search_hits_batch would run the requests -- one dict per request: kind (0
     fused, 1 fallback), its pass, its window (how many drains precede it) and its region (offset,
-    slots) of the device hit buffer (mh_hits_batch_regions)."""
+    slots) of the device hit buffer (mh_hits_batch_regions).  fuse_fast=True: how
+    search_hits_batch(fuse_fast=True) would, kind and pass following batch_plan_ex
+    (mh_hits_batch_regions_ex; `flags` overrides the flag word)."""
     requests = list(requests)
     arr, keep, _, _ = _hits_requests(requests, cap)
     buf = (mh_hits_region * max(1, len(requests)))()
-    k = lib.mh_hits_batch_regions(arr, len(requests), buf, len(requests))
+    if fuse_fast or flags is not None:
+        k = lib.mh_hits_batch_regions_ex(arr, len(requests), MH_BATCH_FUSE_FAST if flags is None else flags, buf,
+                                         len(requests))
+    else:
+        k = lib.mh_hits_batch_regions(arr, len(requests), buf, len(requests))
     if k < 0:
         _check(k)
     return [{f: getattr(buf[i], f) for f, _ in mh_hits_region._fields_ if f != "reserved"} for i in range(k)]

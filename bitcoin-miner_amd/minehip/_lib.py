@@ -39,7 +39,7 @@ EXPORTS = (
     "mh_multi_rates", "mh_search_batch", "mh_batch_plan", "mh_miner_handle_batch",
     "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
     "mh_search_hits_batch", "mh_hits_batch_regions", "mh_search_batch_ex", "mh_batch_plan_ex",
-    "mh_search_first_batch_ex", "mh_first_batch_order_ex",
+    "mh_search_first_batch_ex", "mh_first_batch_order_ex", "mh_search_hits_batch_ex", "mh_hits_batch_regions_ex",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -206,6 +206,10 @@ def _load():
                                           ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64]
     L.mh_search_hits_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hit), sz,
                                        ctypes.POINTER(mh_hits_result)]
+    L.mh_search_hits_batch_ex.argtypes = [ctypes.c_int, ctypes.POINTER(mh_hits_request), sz, ctypes.c_uint32,
+                                          ctypes.POINTER(mh_hit), sz, ctypes.POINTER(mh_hits_result)]
+    L.mh_hits_batch_regions_ex.argtypes = [ctypes.POINTER(mh_hits_request), sz, ctypes.c_uint32,
+                                           ctypes.POINTER(mh_hits_region), ctypes.c_int64]
     L.mh_hits_batch_regions.argtypes = [ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hits_region),
                                         ctypes.c_int64]
     L.mh_batch_plan.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_batch_item), ctypes.c_int64]
@@ -237,7 +241,7 @@ def _load():
     restype = {"mh_plan": ctypes.c_int64, "mh_multi_plan": ctypes.c_int64, "mh_batch_plan": ctypes.c_int64,
                "mh_batch_plan_ex": ctypes.c_int64,
                "mh_first_batch_order": ctypes.c_int64, "mh_hits_batch_regions": ctypes.c_int64,
-               "mh_first_batch_order_ex": ctypes.c_int64,
+               "mh_first_batch_order_ex": ctypes.c_int64, "mh_hits_batch_regions_ex": ctypes.c_int64,
                "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
                "mh_sched_destroy": None, "mh_server_destroy": None}

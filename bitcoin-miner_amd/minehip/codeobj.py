@@ -59,6 +59,15 @@ def batch_first_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def batch_hits_code_object():
+    """The embedded code object of the hits batch kernels (mh_search_hits_batch_ex):
+    batch_hits<J, MODE>, fast_search.hip built with -DMH_BATCH -DMH_HITS
+    (mh_batch_hits_co_begin .. mh_batch_hits_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_hits_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_hits_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def unpack_msgpack(b):
     """Decode one MessagePack object (the subset AMDGPU metadata uses: maps, arrays, strings,
     binary, integers, floats, booleans, nil).  No dependency on the msgpack package."""
@@ -180,3 +189,9 @@ def batch_first_kernel_resources(co=None):
     """The same of the embedded batch_first<J, MODE> kernels (or of those of code object `co`)."""
     return fast_kernel_resources(batch_first_code_object() if co is None else co,
                                  r"_ZN2mh11batch_firstILi(\d+)ELi(\d+)E")
+
+
+def batch_hits_kernel_resources(co=None):
+    """The same of the embedded batch_hits<J, MODE> kernels (or of those of code object `co`)."""
+    return fast_kernel_resources(batch_hits_code_object() if co is None else co,
+                                 r"_ZN2mh10batch_hitsILi(\d+)ELi(\d+)E")

@@ -313,6 +313,31 @@ typedef struct mh_hits_result {
 int mh_search_hits_batch(int dev, const mh_hits_request *reqs, size_t n, mh_hit *hits, size_t hits_cap,
                          mh_hits_result *out);
 
+/* mh_search_hits_batch with flags.  flags == 0 is exactly mh_search_hits_batch; an unknown flag bit
+ * returns MH_EINVAL.  MH_BATCH_FUSE_FAST (the only flag) also fuses the requests whose plan holds
+ * fast pieces, exactly as mh_search_batch_ex decides it (the plan is mh_batch_plan_ex's: the same
+ * fused / fallback split, passes, slots, launches, lane rule and cap, MH_BATCH_FAST_MAX_NONCES;
+ * targets and caps play no part).  The fast pieces of one layout <J, MODE> of a pass run as one
+ * launch of the batch_hits<J, MODE> kernel -- the per-nonce loop and the append of mh_search_hits,
+ * one workgroup per 256-run chunk of a table of pieces -- behind the pass's batch_scan_hits launch
+ * on the same stream: the fast pieces and the generic tiles of one request append through one
+ * cursor into one region of the device hit buffer and write the request's one slot segment.  Every
+ * chunk runs (the count needs every nonce); no workgroup waits for another.  A pass is one copy of
+ * tables, its launches, one segmented merge and one copy-back; windows, drains, region sizes and
+ * rebuilds are mh_search_hits_batch's (mh_hits_batch_regions_ex shows the schedule), the items and
+ * per-chunk tables counting against the table buffer a window's passes share; rebuilds and
+ * fallbacks run through the mh_search_hits path after the fused passes, a list cut by its cap
+ * (0 < cap < count) from a prefix of the range sized by the fused scan's count for cap hits.
+ * For every request whose status is MH_OK: count, stored, hash, nonce and the `stored` entries at
+ * hits + offset are bit for bit mh_search_hits', whatever the batch holds, the lanes, the passes,
+ * the fused / fallback split, the size of the device hit buffer or the timing.  offset, the
+ * per-request statuses and the call's errors are mh_search_hits_batch's.  Measured
+ * (profiles/hits_batch_fast_latency.json): no size up to 8 x 10^9 nonces is slower
+ * fused than the fallback loop by more than that loop's own spread, so the cap stays
+ * MH_BATCH_FAST_MAX_NONCES.  Additive in ABI 5. */
+int mh_search_hits_batch_ex(int dev, const mh_hits_request *reqs, size_t n, uint32_t flags, mh_hit *hits,
+                            size_t hits_cap, mh_hits_result *out);
+
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
 
@@ -500,6 +525,13 @@ typedef struct mh_hits_region {
  * there are more than cap (the first cap written, as mh_plan), or the MH_E* of the first request
  * mh_search_hits_batch would refuse.  n == 0 returns 0. */
 int64_t mh_hits_batch_regions(const mh_hits_request *reqs, size_t n, mh_hits_region *out, int64_t cap);
+
+/* mh_hits_batch_regions for mh_search_hits_batch_ex(flags): flags == 0 is mh_hits_batch_regions; an
+ * unknown flag bit returns MH_EINVAL.  With MH_BATCH_FUSE_FAST kind and pass follow
+ * mh_batch_plan_ex: kind 0 for a fused request (its pieces there have kind 0 or 2) with the pass
+ * of its pieces, kind 1 for a fallback. */
+int64_t mh_hits_batch_regions_ex(const mh_hits_request *reqs, size_t n, uint32_t flags, mh_hits_region *out,
+                                 int64_t cap);
 
 /* One span of mh_search_multi's adaptive split (chunk == 0), ABI 4. */
 typedef struct mh_span {
