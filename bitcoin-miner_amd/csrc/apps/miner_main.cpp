@@ -8,13 +8,20 @@
 // The scan is libminehip's mh_miner_handle over every visible GPU (one miner
 // process per GPU: HIP_VISIBLE_DEVICES).  When more Requests are already queued
 // on the connection (up to 64), they go together through
-// mh_miner_handle_batch -- the small ones in one fused GPU pass -- and their
+// mh_miner_handle_batch_ex -- the small ones in one fused GPU pass -- and their
 // Results are written in arrival order.  LSP is liblsp440 (wire compatible
 // with the reference's lsp package, include/lsp440.h).
 //
 //   minehip-miner <hostport>     the miner over LSP
 //   minehip-miner --stdio        the per-message step alone: one JSON
 //                                Message per stdin line -> Result line
+//
+// Environment:
+//   MINEHIP_MINER_FUSE_FAST=1    batches go through mh_miner_handle_batch_ex(MH_BATCH_FUSE_FAST): the
+//                                fast pieces of queued Requests of up to 10^9 nonces fuse too
+//   MINEHIP_MINER_STATS=1        on exit, one line to stderr:
+//                                minehip-miner: requests=<n> batches=<n> largest=<n>
+//                                (payloads read, handle calls made, most payloads in one call)
 #include <stdio.h>
 #include <string.h>
 
@@ -28,6 +35,11 @@
 namespace {
 
 constexpr size_t kMaxBatch = 64;  // payloads taken from the connection's queue for one batch
+
+bool env_on(const char* name) {
+    const char* e = getenv(name);
+    return e && !strcmp(e, "1");
+}
 
 std::vector<int> all_devices() {
     std::vector<int> d;
@@ -68,6 +80,8 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
         lsp_client_close(c);
         return 1;
     }
+    const uint32_t flags = env_on("MINEHIP_MINER_FUSE_FAST") ? (uint32_t)MH_BATCH_FUSE_FAST : 0u;
+    unsigned long long n_requests = 0, n_batches = 0, largest = 0;
     std::vector<uint8_t> buf(1 << 16);
     char out[256];
     int status = 0;
@@ -80,7 +94,7 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
             continue;
         }
         if (rc != LSP_OK) break;  // server lost or closed: the miner is done
-        // What the connection already holds goes to the GPU as one batch (mh_miner_handle_batch:
+        // What the connection already holds goes to the GPU as one batch (mh_miner_handle_batch_ex:
         // the small Requests in one fused pass) instead of one blocking search each.  A read that
         // finds nothing (or the connection's end, which the next blocking read reports) ends it.
         more.clear();
@@ -95,6 +109,9 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
             if (r2 != LSP_OK) break;
             more.emplace_back((const char*)b2.data(), n2);
         }
+        n_requests += more.size() + 1;
+        n_batches += 1;
+        if (more.size() + 1 > largest) largest = more.size() + 1;
         if (more.empty()) {  // one payload: the single-request path
             size_t on = 0;
             const int hr = mh_miner_handle(devs.data(), (int)devs.size(), (const char*)buf.data(), n, out, sizeof out,
@@ -122,8 +139,8 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
             ptrs[i] = more[i - 1].data();
             lens[i] = more[i - 1].size();
         }
-        const int hr = mh_miner_handle_batch(devs.data(), (int)devs.size(), ptrs.data(), lens.data(), k, outs.data(),
-                                             sizeof out, olens.data(), st.data());
+        const int hr = mh_miner_handle_batch_ex(devs.data(), (int)devs.size(), ptrs.data(), lens.data(), k, flags,
+                                                outs.data(), sizeof out, olens.data(), st.data());
         bool stop = false;
         for (size_t i = 0; i < k && !stop && hr == MH_OK; ++i) {  // Results in arrival order
             if (st[i] == MH_ENOTREQ || st[i] == MH_ERANGE) {
@@ -146,6 +163,8 @@ int run_lsp(const char* hostport, const std::vector<int>& devs) {
         if (stop) break;
     }
     lsp_client_close(c);
+    if (env_on("MINEHIP_MINER_STATS"))
+        fprintf(stderr, "minehip-miner: requests=%llu batches=%llu largest=%llu\n", n_requests, n_batches, largest);
     return status;
 }
 

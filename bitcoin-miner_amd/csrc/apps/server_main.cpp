@@ -7,6 +7,13 @@
 // reassignment, lexicographic-min merge); this file only moves its messages
 // over liblsp440 and reports lost connections to it (the N3 fix: the
 // reference's lsp server never surfaces a lost client to Read).
+//
+// Environment (the arguments, usage line and output stay the reference's):
+//   MINEHIP_CHUNK        fixed chunk size (tests)
+//   MINEHIP_QUEUE_DEPTH  most chunks one miner holds at once, 1..64 (default 1): above 1 the small
+//                        Requests of many clients queue on a miner, which runs them as one batch
+//   MINEHIP_QUEUE_NS     work one miner may hold, as nanoseconds at its measured rate
+//                        (default 0: one chunk's target time)
 #include <stdio.h>
 
 #include <string>
@@ -53,6 +60,22 @@ int main(int argc, char** argv) {
         printf("Port must be a number: %s\n", argv[1]);
         return 2;
     }
+    mh_sched_queue_opts q;
+    mh_sched_default_queue_opts(&q);
+    if (const char* e = getenv("MINEHIP_QUEUE_DEPTH")) {
+        uint64_t d = 0;
+        if (!apps::parse_u64(e, &d) || d < 1 || d > MH_SCHED_MAX_DEPTH) {
+            printf("bad MINEHIP_QUEUE_DEPTH: %s (1..%d)\n", e, MH_SCHED_MAX_DEPTH);
+            return 2;
+        }
+        q.depth = (uint32_t)d;
+    }
+    if (const char* e = getenv("MINEHIP_QUEUE_NS")) {
+        if (!apps::parse_u64(e, &q.queue_ns)) {
+            printf("bad MINEHIP_QUEUE_NS: %s\n", e);
+            return 2;
+        }
+    }
     const lsp_params p = apps::params_from_env();
     lsp_server* s = nullptr;
     const int rc = lsp_server_new((int)port, &p, &s);
@@ -65,7 +88,7 @@ int main(int argc, char** argv) {
     if (const char* e = getenv("MINEHIP_CHUNK")) {  // fixed chunk size (tests)
         o.init_chunk = o.min_chunk = o.max_chunk = strtoull(e, nullptr, 10);
     }
-    mh_server* v = mh_server_create(&o);
+    mh_server* v = mh_server_create_ex(&o, &q);
     if (!v) {
         printf("bad MINEHIP_CHUNK\n");
         return 2;

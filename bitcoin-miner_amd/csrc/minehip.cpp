@@ -1743,6 +1743,35 @@ int hits_batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const mh_hits
     return rc;
 }
 
+// mh_search_batch_ex(MH_BATCH_FUSE_FAST) over n >= 1 requests, the fallbacks through `fallback`.
+int search_batch_ex_impl(int dev, const mh_request* reqs, size_t n, mh_result* out, const BatchFallback& fallback) {
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    batch_requests(reqs, n, &status, &valid);
+    for (size_t i = 0; i < n; ++i) out[i] = mh_result{status[i], 0, 0, 0};
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    mh::plan_batch_ex(valid.data(), valid.size(), plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(),
+                      &pieces, &args);
+    int passes = 0;
+    for (const mh::BatchPiece& p : pieces)
+        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
+    if (passes) {
+        const int rc = batch_run_fused_ex(dev, valid.data(), pieces, args, passes, slot_cap, out);
+        if (rc) return rc;
+    }
+    for (const mh::BatchPiece& p : pieces) {  // the fallbacks, after the fused passes
+        if (p.kind != 1) continue;
+        const mh::BatchRequest& r = valid[p.idx];
+        const int rc = fallback(r, &out[r.id].hash, &out[r.id].nonce);
+        if (rc) return rc;
+    }
+    return MH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1884,31 +1913,9 @@ int mh_search_batch_ex(int dev, const mh_request* reqs, size_t n, uint32_t flags
     if (!(flags & MH_BATCH_FUSE_FAST)) return mh_search_batch(dev, reqs, n, out);
     if (n == 0) return MH_OK;
     if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
-    std::vector<int> status;
-    std::vector<mh::BatchRequest> valid;
-    batch_requests(reqs, n, &status, &valid);
-    for (size_t i = 0; i < n; ++i) out[i] = mh_result{status[i], 0, 0, 0};
-    if (valid.empty()) return MH_OK;
-    g_err.clear();
-    const uint32_t slot_cap = batch_slots();
-    std::vector<mh::BatchPiece> pieces;
-    std::vector<mh::FastArgs> args;
-    mh::plan_batch_ex(valid.data(), valid.size(), plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(),
-                      &pieces, &args);
-    int passes = 0;
-    for (const mh::BatchPiece& p : pieces)
-        if (p.kind != 1) passes = std::max(passes, p.pass + 1);
-    if (passes) {
-        const int rc = batch_run_fused_ex(dev, valid.data(), pieces, args, passes, slot_cap, out);
-        if (rc) return rc;
-    }
-    for (const mh::BatchPiece& p : pieces) {  // the fallbacks, after the fused passes
-        if (p.kind != 1) continue;
-        const mh::BatchRequest& r = valid[p.idx];
-        const int rc = search_impl(dev, r.pre, r.lower, r.upper, &out[r.id].hash, &out[r.id].nonce);
-        if (rc) return rc;
-    }
-    return MH_OK;
+    return search_batch_ex_impl(dev, reqs, n, out, [dev](const mh::BatchRequest& r, uint64_t* h, uint64_t* nn) {
+        return search_impl(dev, r.pre, r.lower, r.upper, h, nn);
+    });
 }
 
 int64_t mh_batch_plan_ex(const mh_request* reqs, size_t n, uint32_t flags, mh_batch_piece* out, int64_t cap) {
@@ -2386,7 +2393,13 @@ int64_t mh_hits_batch_regions_ex(const mh_hits_request* reqs, size_t n, uint32_t
 
 int mh_miner_handle_batch(const int* devs, int ndev, const char* const* requests, const size_t* lens, size_t n,
                           char* out, size_t cap_each, size_t* out_lens, int* status) {
+    return mh_miner_handle_batch_ex(devs, ndev, requests, lens, n, 0, out, cap_each, out_lens, status);
+}
+
+int mh_miner_handle_batch_ex(const int* devs, int ndev, const char* const* requests, const size_t* lens, size_t n,
+                             uint32_t flags, char* out, size_t cap_each, size_t* out_lens, int* status) {
     g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
     if (n == 0) return MH_OK;
     if (!devs || ndev <= 0 || !requests || !lens || !status) return fail(MH_EINVAL, "bad arguments");
     std::vector<mh::Msg> msgs(n);
@@ -2413,12 +2426,14 @@ int mh_miner_handle_batch(const int* devs, int ndev, const char* const* requests
     std::vector<mh_result> res(reqs.size());
     // fallbacks as mh_miner_handle searches: one device through mh_search's path, several through
     // mh_search_multi's adaptive split
-    const int rc = search_batch_impl(
-        devs[0], reqs.data(), reqs.size(), res.data(), [&](const mh::BatchRequest& r, uint64_t* h, uint64_t* nn) {
-            if (ndev == 1) return search_impl(devs[0], r.pre, r.lower, r.upper, h, nn);
-            const mh_request& q = reqs[r.id];
-            return mh_search_multi(devs, ndev, q.msg, q.len, q.lower, q.upper, 0, h, nn);
-        });
+    const BatchFallback fallback = [&](const mh::BatchRequest& r, uint64_t* h, uint64_t* nn) {
+        if (ndev == 1) return search_impl(devs[0], r.pre, r.lower, r.upper, h, nn);
+        const mh_request& q = reqs[r.id];
+        return mh_search_multi(devs, ndev, q.msg, q.len, q.lower, q.upper, 0, h, nn);
+    };
+    const int rc = (flags & MH_BATCH_FUSE_FAST)
+                       ? search_batch_ex_impl(devs[0], reqs.data(), reqs.size(), res.data(), fallback)
+                       : search_batch_impl(devs[0], reqs.data(), reqs.size(), res.data(), fallback);
     if (rc) return rc;
     for (size_t k = 0; k < reqs.size(); ++k) {
         const size_t i = where[k];

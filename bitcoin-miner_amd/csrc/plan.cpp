@@ -103,6 +103,29 @@ void absorb_prefix(const uint8_t* msg, size_t len, Prefix* out) {
     }
 }
 
+uint64_t host_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
+    Prefix pre;
+    absorb_prefix(msg, len, &pre);
+    uint8_t buf[128] = {0};  // tail (< 64) + digits (<= 20) + 0x80 + length (8): one or two blocks
+    memcpy(buf, pre.tail, pre.t);
+    const int d = decimal_digits(nonce);
+    for (int i = d - 1; i >= 0; --i, nonce /= 10u) buf[pre.t + (uint32_t)i] = (uint8_t)('0' + nonce % 10u);
+    const uint32_t used = pre.t + (uint32_t)d;
+    buf[used] = 0x80;
+    const uint32_t total = used + 9u <= 64u ? 64u : 128u;
+    const uint64_t bits = (pre.plen + (uint64_t)d) * 8u;
+    for (int i = 0; i < 8; ++i) buf[total - 1u - (uint32_t)i] = (uint8_t)(bits >> (8 * i));
+    for (uint32_t blk = 0; blk < total; blk += 64u) {
+        uint32_t w[16];
+        for (int i = 0; i < 16; ++i) {
+            const uint8_t* p = buf + blk + 4 * i;
+            w[i] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3];
+        }
+        host_compress(pre.mid, w);
+    }
+    return (uint64_t)pre.mid[0] << 32 | pre.mid[1];
+}
+
 void make_gen_args(const Prefix& pre, GenArgs* ga) {
     memset(ga, 0, sizeof *ga);
     memcpy(ga->mid, pre.mid, sizeof pre.mid);

@@ -31,6 +31,11 @@ void absorb_prefix(const uint8_t* msg, size_t len, Prefix* out);
 // padding-only block).
 void host_compress(uint32_t st[8], const uint32_t w16[16]);
 
+// Hash(msg, nonce) of bitcoin/hash.go:13-17 on the host: one or two compressions past the
+// prefix.  Not a search path (there is no CPU fallback): the scheduler checks one miner Result
+// with it when miners hold several chunks (sched.hpp).
+uint64_t host_hash(const uint8_t* msg, size_t len, uint64_t nonce);
+
 // One launch of the plan.
 struct Piece {
     uint64_t first;   // first nonce

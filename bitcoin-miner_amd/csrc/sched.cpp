@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/minehip.h"
 
@@ -92,30 +93,60 @@ bool Scheduler::take(Job& j, uint64_t c, uint64_t* lo, uint64_t* hi) {
     return true;
 }
 
+bool Scheduler::valid_queue_opts(const mh_sched_queue_opts& q) {
+    return q.depth >= 1 && q.depth <= MH_SCHED_MAX_DEPTH && q.reserved == 0;
+}
+
+void Scheduler::set_queue(const mh_sched_queue_opts& q, HostHash hash) {
+    std::lock_guard<std::mutex> lk(mu_);
+    q_ = q;
+    hash_ = hash;
+}
+
+// May m be handed another chunk?  Idle: always.  Otherwise while it holds fewer than depth chunks
+// and fewer nonces than it works off in queue_ns -- a large job's chunk (rate x target_ns) fills
+// that alone, so only small jobs stack up.
+bool Scheduler::eligible(const Miner& m) const {
+    if (m.q.empty()) return true;
+    if (m.q.size() >= q_.depth) return false;
+    const double ns = (double)(q_.queue_ns ? q_.queue_ns : o_.target_ns);
+    const double budget = m.rate > 0.0 ? m.rate * ns : (double)o_.init_chunk;
+    return (double)m.held < std::floor(budget);  // whole nonces, as chunk_size cuts them
+}
+
+// A chunk that will not be answered goes back to the front of its job (a cancelled job only
+// counts it off).
+void Scheduler::requeue_chunk(const Chunk& c) {
+    Job* j = find_job(c.job);
+    if (!j) return;
+    j->outstanding -= 1u;
+    if (!j->cancelled) {
+        j->requeue.emplace_front(c.lo, c.hi);
+        st_.chunks_requeued += 1u;
+    } else if (j->outstanding == 0) {
+        erase_job(j->id);
+    }
+}
+
+// Miner i is gone: its chunks go back, newest first, so that the oldest ends up at the front.
+void Scheduler::drop_miner(size_t i) {
+    Miner& m = miners_[i];
+    for (auto it = m.q.rbegin(); it != m.q.rend(); ++it) requeue_chunk(*it);
+    miners_.erase(miners_.begin() + (ptrdiff_t)i);
+}
+
 int Scheduler::add_miner(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
     if (find_miner(id)) return set_error(MH_EINVAL, "miner already joined");
-    miners_.push_back(Miner{id, false, -1, 0, 0, 0, 0.0});
+    miners_.push_back(Miner{id, {}, 0, 0, 0.0, 0, 0.0});
     return MH_OK;
 }
 
 int Scheduler::remove_miner(int64_t id) {
     std::lock_guard<std::mutex> lk(mu_);
     for (size_t i = 0; i < miners_.size(); ++i) {
-        Miner& m = miners_[i];
-        if (m.id != id) continue;
-        if (m.busy) {
-            if (Job* j = find_job(m.job)) {
-                j->outstanding -= 1u;
-                if (!j->cancelled) {
-                    j->requeue.emplace_front(m.lo, m.hi);
-                    st_.chunks_requeued += 1u;
-                } else if (j->outstanding == 0) {
-                    erase_job(j->id);
-                }
-            }
-        }
-        miners_.erase(miners_.begin() + (ptrdiff_t)i);
+        if (miners_[i].id != id) continue;
+        drop_miner(i);
         return MH_OK;
     }
     return set_error(MH_EINVAL, "unknown miner");
@@ -165,13 +196,12 @@ int Scheduler::next(int64_t miner, uint64_t now_ns, mh_assignment* out) {
     if (miner >= 0) {
         m = find_miner(miner);
         if (!m) return set_error(MH_EINVAL, "unknown miner");
-        if (m->busy) return 0;
+        if (!eligible(*m)) return 0;
     } else {
+        // the eligible miner with the fewest chunks out, ties in join order: every miner gets its
+        // first chunk before any gets a second
         for (auto& x : miners_)
-            if (!x.busy) {
-                m = &x;
-                break;
-            }
+            if (eligible(x) && (!m || x.q.size() < m->q.size())) m = &x;
         if (!m) return 0;
     }
     const size_t nj = jobs_.size();
@@ -183,11 +213,9 @@ int Scheduler::next(int64_t miner, uint64_t now_ns, mh_assignment* out) {
         if (!take(j, chunk_size(*m, j), &lo, &hi)) continue;
         rr_ = (idx + 1) % nj;
         j.outstanding += 1u;
-        m->busy = true;
-        m->job = j.id;
-        m->lo = lo;
-        m->hi = hi;
-        m->t0 = now_ns;
+        if (m->q.empty()) m->t_busy = now_ns;
+        m->q.push_back(Chunk{j.id, lo, hi});
+        m->held += (u128)(hi - lo) + 1u;
         st_.chunks_assigned += 1u;
         out->miner = m->id;
         out->job = j.id;
@@ -207,30 +235,58 @@ int Scheduler::job_msg(int64_t job, std::string* out) {
     return MH_OK;
 }
 
+int Scheduler::miner_queue(int64_t miner, std::vector<mh_assignment>* out) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Miner* m = find_miner(miner);
+    if (!m) return set_error(MH_EINVAL, "unknown miner");
+    out->clear();
+    for (const Chunk& c : m->q) {
+        Job* j = find_job(c.job);
+        out->push_back(mh_assignment{m->id, c.job, c.lo, c.hi, j ? j->msg.size() : 0});
+    }
+    return MH_OK;
+}
+
 int Scheduler::result(int64_t miner, uint64_t hash, uint64_t nonce, uint64_t now_ns, mh_completion* out) {
     std::lock_guard<std::mutex> lk(mu_);
     Miner* m = find_miner(miner);
-    if (!m || !m->busy) return set_error(MH_EINVAL, "Result from a miner with no chunk out");
-    m->busy = false;
-    Job* j = find_job(m->job);
-    if (!j) return 0;  // cannot happen: a job lives while chunks are out
-    if (nonce < m->lo || nonce > m->hi) {
-        j->outstanding -= 1u;
-        if (!j->cancelled) {
-            j->requeue.emplace_front(m->lo, m->hi);
-            st_.chunks_requeued += 1u;
-        } else if (j->outstanding == 0) {
-            erase_job(j->id);
+    if (!m || m->q.empty()) return set_error(MH_EINVAL, "Result from a miner with no chunk out");
+    const Chunk c = m->q.front();  // a Result carries no id: it answers the oldest chunk
+    Job* j = find_job(c.job);
+    if (q_.depth > 1) {
+        // Several chunks out: a miner that skipped or reordered an answer would have every later
+        // Result credited to the wrong chunk, and the nonce test cannot see that when clients ask
+        // for the same range with different Data.  The hash ties the Result to this job's Data.
+        const bool ok = j && nonce >= c.lo && nonce <= c.hi && hash_ &&
+                        hash_((const uint8_t*)j->msg.data(), j->msg.size(), nonce) == hash;
+        if (!ok) {
+            drop_miner((size_t)(m - miners_.data()));
+            return set_error(MH_EREJECTED, "Result does not answer the miner's oldest chunk; miner removed");
         }
+    }
+    m->q.pop_front();
+    m->held -= (u128)(c.hi - c.lo) + 1u;
+    if (!j) return 0;  // cannot happen: a job lives while chunks are out
+    if (nonce < c.lo || nonce > c.hi) {
+        requeue_chunk(c);  // depth 1 only: the miner stays, idle
         return set_error(MH_ERANGE, "Result nonce outside the miner's chunk");
     }
-    const double cnt = (double)(m->hi - m->lo) + 1.0;
-    if (now_ns > m->t0) {
-        const double r = cnt / (double)(now_ns - m->t0);
-        m->rate = m->rate > 0.0 ? 0.5 * m->rate + 0.5 * r : r;
+    // Rate: nonces completed over the time the miner was busy with them.  Results of one batch
+    // arrive in a burst, so samples are folded when the queue runs empty or spans target_ns, not
+    // per Result; with one chunk out this is one sample per chunk, cnt / (now - t0).
+    m->acc_nonces += (double)(c.hi - c.lo) + 1.0;
+    if (now_ns > m->t_busy) m->acc_ns += now_ns - m->t_busy;
+    m->t_busy = now_ns;
+    if (m->q.empty() || m->acc_ns >= o_.target_ns) {
+        if (m->acc_ns > 0) {
+            const double r = m->acc_nonces / (double)m->acc_ns;
+            m->rate = m->rate > 0.0 ? 0.5 * m->rate + 0.5 * r : r;
+        }
+        m->acc_nonces = 0.0;
+        m->acc_ns = 0;
     }
     st_.chunks_done += 1u;
-    st_.nonces_done += m->hi - m->lo + 1u;  // wraps only for a single 2^64 chunk
+    st_.nonces_done += c.hi - c.lo + 1u;  // wraps only for a single 2^64 chunk
     j->outstanding -= 1u;
     if (!j->cancelled && lex_less(hash, nonce, j->best_hash, j->best_nonce)) {
         j->best_hash = hash;
@@ -257,7 +313,7 @@ void Scheduler::stats(mh_sched_stats* out) {
     *out = st_;
     out->miners = miners_.size();
     out->idle_miners = 0;
-    for (const auto& m : miners_) out->idle_miners += m.busy ? 0u : 1u;
+    for (const auto& m : miners_) out->idle_miners += m.q.empty() ? 1u : 0u;
     out->jobs = jobs_.size();
 }
 
@@ -267,11 +323,6 @@ bool Scheduler::idle_jobs() {
 }
 
 }  // namespace mh
-
-struct mh_sched {
-    mh::Scheduler s;
-    explicit mh_sched(const mh_sched_opts& o) : s(o) {}
-};
 
 extern "C" {
 
@@ -292,6 +343,13 @@ mh_sched* mh_sched_create(const mh_sched_opts* opts) {
         return nullptr;
     }
     return new mh_sched(o);
+}
+
+void mh_sched_default_queue_opts(mh_sched_queue_opts* q) {
+    if (!q) return;
+    q->depth = 1;
+    q->reserved = 0;
+    q->queue_ns = 0;
 }
 
 void mh_sched_destroy(mh_sched* s) { delete s; }
@@ -334,6 +392,21 @@ int mh_sched_job_msg(mh_sched* s, int64_t job, uint8_t* buf, size_t cap, size_t*
     if (m.size() > cap || (!buf && !m.empty())) return mh::set_error(MH_ETOOLONG, "buffer too small");
     if (!m.empty()) memcpy(buf, m.data(), m.size());
     return MH_OK;
+}
+
+int64_t mh_sched_miner_queue(mh_sched* s, int64_t miner, mh_assignment* out, int64_t cap) {
+    MH_NEED(s);
+    if (cap < 0) return mh::set_error(MH_EINVAL, "cap < 0");
+    std::vector<mh_assignment> q;
+    const int rc = s->s.miner_queue(miner, &q);
+    if (rc) return rc;
+    int64_t k = 0;
+    for (const mh_assignment& a : q) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = a;
+        ++k;
+    }
+    return k;
 }
 
 int mh_sched_result(mh_sched* s, int64_t miner, uint64_t hash, uint64_t nonce, uint64_t now_ns,

@@ -20,6 +20,7 @@
 
 #include "../../include/minehip.h"
 #include "msgcodec.hpp"
+#include "plan.hpp"
 #include "sched.hpp"
 
 struct mh_server {
@@ -29,7 +30,7 @@ struct mh_server {
     std::deque<std::pair<int64_t, std::string>> out;
     explicit mh_server(const mh_sched_opts& o) : s(o) {}
 
-    // hand every idle miner a chunk
+    // hand out chunks until no miner may take another
     int dispatch(uint64_t now) {
         mh_assignment a;
         for (;;) {
@@ -44,17 +45,49 @@ struct mh_server {
     }
 };
 
+namespace {
+
+// The options of the _ex constructors: NULL = defaults; false (MH_EINVAL) when either is bad.
+bool resolve_opts(const mh_sched_opts* opts, const mh_sched_queue_opts* q, mh_sched_opts* o, mh_sched_queue_opts* qo) {
+    mh_sched_default_opts(o);
+    mh_sched_default_queue_opts(qo);
+    if (opts) *o = *opts;
+    if (q) *qo = *q;
+    if (!mh::Scheduler::valid_opts(*o)) {
+        mh::set_error(MH_EINVAL, "bad scheduler options");
+        return false;
+    }
+    if (!mh::Scheduler::valid_queue_opts(*qo)) {
+        mh::set_error(MH_EINVAL, "bad queue options: depth must be 1..MH_SCHED_MAX_DEPTH, reserved 0");
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
 extern "C" {
 
-mh_server* mh_server_create(const mh_sched_opts* opts) {
+// Here and not in sched.cpp: the queueing scheduler checks Results with plan.cpp's host Hash, and
+// sched.cpp alone stays free of that dependency.
+mh_sched* mh_sched_create_ex(const mh_sched_opts* opts, const mh_sched_queue_opts* q) {
     mh_sched_opts o;
-    mh_sched_default_opts(&o);
-    if (opts) o = *opts;
-    if (!mh::Scheduler::valid_opts(o)) {
-        mh::set_error(MH_EINVAL, "bad scheduler options");
-        return nullptr;
-    }
-    return new mh_server(o);
+    mh_sched_queue_opts qo;
+    if (!resolve_opts(opts, q, &o, &qo)) return nullptr;
+    mh_sched* s = new mh_sched(o);
+    s->s.set_queue(qo, &mh::host_hash);
+    return s;
+}
+
+mh_server* mh_server_create(const mh_sched_opts* opts) { return mh_server_create_ex(opts, nullptr); }
+
+mh_server* mh_server_create_ex(const mh_sched_opts* opts, const mh_sched_queue_opts* q) {
+    mh_sched_opts o;
+    mh_sched_queue_opts qo;
+    if (!resolve_opts(opts, q, &o, &qo)) return nullptr;
+    mh_server* v = new mh_server(o);
+    v->s.set_queue(qo, &mh::host_hash);
+    return v;
 }
 
 void mh_server_destroy(mh_server* v) { delete v; }
@@ -83,6 +116,7 @@ int mh_server_read(mh_server* v, int64_t conn, const char* payload, size_t len, 
             const int r = v->s.result(conn, m.hash, m.nonce, now_ns, &c);
             if (r < 0) {
                 rc = r;
+                if (r == MH_EREJECTED) v->miners.erase(conn);  // the scheduler removed it as lost
             } else if (r == 1) {
                 v->out.emplace_back(c.client, mh::encode(2, nullptr, 0, 0, 0, c.hash, c.nonce));
             }
@@ -91,7 +125,7 @@ int mh_server_read(mh_server* v, int64_t conn, const char* payload, size_t len, 
         default:
             rc = mh::set_error(MH_EINVAL, "unknown message type");
     }
-    // a rejected Result requeued its chunk: hand the work out again either way
+    // a rejected Result requeued its chunk(s): hand the work out again either way
     const int d = v->dispatch(now_ns);
     return rc ? rc : d;
 }

@@ -19,7 +19,10 @@ tests read like the reference (line numbers into the reference repo):
   search_hits_batch(requests, cap=4096)
                              every hit of many small requests in one GPU pass
                              (fuse_fast=True: the fast pieces of larger ones too)
-  miner_handle_batch(...)    miner_handle for the payloads a miner holds at once
+  miner_handle_batch(...)    miner_handle for the payloads a miner holds at once (fuse_fast=True:
+                             the fast pieces of the larger Requests fuse too)
+  Scheduler / Server         the server's chunk scheduler and message loop (depth=: how many
+                             chunks a miner may hold at once, so small Requests reach it as a batch)
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
   miner_handle(request)      one miner step: Request payload -> Result payload
@@ -478,11 +481,13 @@ def miner_handle(request_payload, devs=(0,)):
     return buf.raw[:need.value]
 
 
-def miner_handle_batch(payloads, devs=(0,), errors="return"):
+def miner_handle_batch(payloads, devs=(0,), errors="return", fuse_fast=False):
     """miner_handle for the payloads a miner holds at once (mh_miner_handle_batch): the valid
-    small Requests run as one fused batch on devs[0].  A list with, per payload, the Result
-    payload or the MinehipError miner_handle would raise (MH_ENOTREQ, MH_ERANGE: a miner skips
-    those); errors="raise" raises the first one instead."""
+    small Requests run as one fused batch on devs[0]; fuse_fast=True also fuses the fast pieces
+    of the larger ones, up to MH_BATCH_FAST_MAX_NONCES nonces each (mh_miner_handle_batch_ex with
+    MH_BATCH_FUSE_FAST).  A list with, per payload, the Result payload or the MinehipError
+    miner_handle would raise (MH_ENOTREQ, MH_ERANGE: a miner skips those); errors="raise" raises
+    the first one instead."""
     if errors not in ("raise", "return"):
         raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
     ps = [_b(p) for p in payloads]
@@ -493,7 +498,11 @@ def miner_handle_batch(payloads, devs=(0,), errors="return"):
     out = ctypes.create_string_buffer(max(1, n) * cap)
     out_lens = (ctypes.c_size_t * max(1, n))()
     status = (ctypes.c_int * max(1, n))()
-    _check(lib.mh_miner_handle_batch(arr, len(devs), reqs, lens, n, out, cap, out_lens, status))
+    if fuse_fast:
+        _check(lib.mh_miner_handle_batch_ex(arr, len(devs), reqs, lens, n, MH_BATCH_FUSE_FAST, out, cap, out_lens,
+                                            status))
+    else:
+        _check(lib.mh_miner_handle_batch(arr, len(devs), reqs, lens, n, out, cap, out_lens, status))
     what = {MH_ENOTREQ: "not a Request", MH_ERANGE: "lower > upper"}
     res = []
     for i in range(n):
@@ -510,6 +519,7 @@ def miner_handle_batch(payloads, devs=(0,), errors="return"):
 
 # ---- bitcoin/server/server.go (stub :62) mirror: include/minehip_server.h ----
 from ._lib import mh_sched_opts, mh_assignment, mh_completion, mh_sched_stats  # noqa: E402
+from ._lib import mh_sched_queue_opts, MH_SCHED_MAX_DEPTH  # noqa: E402,F401
 
 
 def _opts(init_chunk=None, min_chunk=None, max_chunk=None, target_ns=None):
@@ -520,6 +530,22 @@ def _opts(init_chunk=None, min_chunk=None, max_chunk=None, target_ns=None):
         if v is not None:
             setattr(o, k, v)
     return o
+
+
+def _queue_opts(depth=None, queue_ns=None):
+    """mh_sched_queue_opts for depth / queue_ns, or None (mh_sched_create's own path) when neither
+    is given.  Values that do not fit the struct's fields raise like the library's MH_EINVAL."""
+    if depth is None and queue_ns is None:
+        return None
+    q = mh_sched_queue_opts()
+    lib.mh_sched_default_queue_opts(ctypes.byref(q))
+    for k, v, top in (("depth", depth, 0xFFFFFFFF), ("queue_ns", queue_ns, U64_MAX)):
+        if v is None:
+            continue
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= top:
+            raise MinehipError(MH_EINVAL, f"{k} = {v!r} is out of range")
+        setattr(q, k, v)
+    return q
 
 
 def _stats(fn, h):
@@ -537,10 +563,17 @@ def _chk_neg(rc):
 class Scheduler:
     """The server's chunk scheduler (mh_sched_*): jobs are client Requests,
     chunks go to miners, Results merge by the lexicographic min.  Times are
-    caller-supplied nanoseconds."""
+    caller-supplied nanoseconds.  depth (1..MH_SCHED_MAX_DEPTH, default 1) is how
+    many chunks one miner may hold at once and queue_ns the work it may hold, as
+    time at its measured rate (0: target_ns) (mh_sched_create_ex)."""
 
-    def __init__(self, **opts):
-        self._h = lib.mh_sched_create(ctypes.byref(_opts(**opts)))
+    def __init__(self, depth=None, queue_ns=None, **opts):
+        self._h = None
+        q = _queue_opts(depth, queue_ns)
+        if q is None:
+            self._h = lib.mh_sched_create(ctypes.byref(_opts(**opts)))
+        else:
+            self._h = lib.mh_sched_create_ex(ctypes.byref(_opts(**opts)), ctypes.byref(q))
         if not self._h:
             _check(MH_EINVAL)
 
@@ -571,6 +604,14 @@ class Scheduler:
             return None
         return a.miner, a.job, a.lower, a.upper
 
+    def queue(self, miner, cap=MH_SCHED_MAX_DEPTH):
+        """[(job, lower, upper), ...]: the chunks `miner` holds, oldest first (mh_sched_miner_queue)."""
+        buf = (mh_assignment * max(1, cap))()
+        k = _chk_neg(lib.mh_sched_miner_queue(self._h, miner, buf, cap))
+        if k > cap:
+            raise ValueError("queue longer than cap")
+        return [(buf[i].job, buf[i].lower, buf[i].upper) for i in range(k)]
+
     def job_msg(self, job):
         n = ctypes.c_size_t()
         buf = ctypes.create_string_buffer(MAX_MSG)
@@ -593,10 +634,16 @@ MAX_MSG = 1 << 20  # MH_MAX_MSG_LEN
 
 class Server:
     """The server's message loop (mh_server_*): feed it what lsp.Server.Read
-    returns, send what writes() yields with lsp.Server.Write."""
+    returns, send what writes() yields with lsp.Server.Write.  depth and
+    queue_ns as Scheduler's (mh_server_create_ex)."""
 
-    def __init__(self, **opts):
-        self._h = lib.mh_server_create(ctypes.byref(_opts(**opts)))
+    def __init__(self, depth=None, queue_ns=None, **opts):
+        self._h = None
+        q = _queue_opts(depth, queue_ns)
+        if q is None:
+            self._h = lib.mh_server_create(ctypes.byref(_opts(**opts)))
+        else:
+            self._h = lib.mh_server_create_ex(ctypes.byref(_opts(**opts)), ctypes.byref(q))
         if not self._h:
             _check(MH_EINVAL)
         self._buf = ctypes.create_string_buffer(4096)  # grown on demand (writes())

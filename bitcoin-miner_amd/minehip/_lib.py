@@ -30,6 +30,7 @@ MH_MAX_WORKERS = 256  # most devices one mh_search_multi / mh_multi_plan call ma
 MH_HITS_MAX_CAP = 1 << 20  # most entries one mh_search_hits call returns
 MH_BATCH_FUSE_FAST = 1     # mh_search_batch_ex / mh_batch_plan_ex flag
 MH_BATCH_FAST_MAX_NONCES = 10 ** 9  # most nonces of a request MH_BATCH_FUSE_FAST fuses
+MH_SCHED_MAX_DEPTH = 64    # include/minehip_server.h: most chunks one miner may hold at once
 
 #: every symbol include/*.h declares
 EXPORTS = (
@@ -40,12 +41,14 @@ EXPORTS = (
     "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
     "mh_search_hits_batch", "mh_hits_batch_regions", "mh_search_batch_ex", "mh_batch_plan_ex",
     "mh_search_first_batch_ex", "mh_first_batch_order_ex", "mh_search_hits_batch_ex", "mh_hits_batch_regions_ex",
+    "mh_miner_handle_batch_ex",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
     "mh_sched_job_msg", "mh_sched_result", "mh_sched_stats_read",
     "mh_server_create", "mh_server_destroy", "mh_server_read", "mh_server_lost",
     "mh_server_pop_write", "mh_server_stats",
+    "mh_sched_default_queue_opts", "mh_sched_create_ex", "mh_server_create_ex", "mh_sched_miner_queue",
 )
 
 
@@ -141,6 +144,10 @@ class mh_sched_opts(ctypes.Structure):
                 ("max_chunk", ctypes.c_uint64), ("target_ns", ctypes.c_uint64)]
 
 
+class mh_sched_queue_opts(ctypes.Structure):
+    _fields_ = [("depth", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("queue_ns", ctypes.c_uint64)]
+
+
 class mh_assignment(ctypes.Structure):
     _fields_ = [("miner", ctypes.c_int64), ("job", ctypes.c_int64), ("lower", ctypes.c_uint64),
                 ("upper", ctypes.c_uint64), ("msg_len", ctypes.c_size_t)]
@@ -219,8 +226,14 @@ def _load():
                                    ctypes.c_int64]
     L.mh_miner_handle_batch.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz,
                                         ctypes.c_char_p, sz, ctypes.POINTER(sz), intp]
+    L.mh_miner_handle_batch_ex.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz,
+                                           ctypes.c_uint32, ctypes.c_char_p, sz, ctypes.POINTER(sz), intp]
     vp = ctypes.c_void_p
     i64 = ctypes.c_int64
+    L.mh_sched_default_queue_opts.argtypes = [ctypes.POINTER(mh_sched_queue_opts)]
+    L.mh_sched_create_ex.argtypes = [ctypes.POINTER(mh_sched_opts), ctypes.POINTER(mh_sched_queue_opts)]
+    L.mh_server_create_ex.argtypes = [ctypes.POINTER(mh_sched_opts), ctypes.POINTER(mh_sched_queue_opts)]
+    L.mh_sched_miner_queue.argtypes = [vp, i64, ctypes.POINTER(mh_assignment), i64]
     L.mh_sched_default_opts.argtypes = [ctypes.POINTER(mh_sched_opts)]
     L.mh_sched_create.argtypes = [ctypes.POINTER(mh_sched_opts)]
     L.mh_sched_destroy.argtypes = [vp]
@@ -244,6 +257,8 @@ def _load():
                "mh_first_batch_order_ex": ctypes.c_int64, "mh_hits_batch_regions_ex": ctypes.c_int64,
                "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
+               "mh_sched_create_ex": vp, "mh_server_create_ex": vp, "mh_sched_default_queue_opts": None,
+               "mh_sched_miner_queue": i64,
                "mh_sched_destroy": None, "mh_server_destroy": None}
     for name in EXPORTS:
         getattr(L, name).restype = restype.get(name, ctypes.c_int)

@@ -387,6 +387,14 @@ int mh_miner_handle(const int *devs, int ndev, const char *request, size_t len, 
 int mh_miner_handle_batch(const int *devs, int ndev, const char *const *requests, const size_t *lens, size_t n,
                           char *out, size_t cap_each, size_t *out_lens, int *status);
 
+/* mh_miner_handle_batch with the flags of mh_search_batch_ex: flags == 0 is mh_miner_handle_batch;
+ * MH_BATCH_FUSE_FAST runs the fused part through mh_search_batch_ex's plan, so queued Requests
+ * of up to MH_BATCH_FAST_MAX_NONCES nonces fuse too (the others still go through
+ * mh_miner_handle's own path, over all listed devices).  Statuses, Results and return code as
+ * mh_miner_handle_batch, bit for bit; an unknown flag bit returns MH_EINVAL. */
+int mh_miner_handle_batch_ex(const int *devs, int ndev, const char *const *requests, const size_t *lens, size_t n,
+                             uint32_t flags, char *out, size_t cap_each, size_t *out_lens, int *status);
+
 /* ---- measurement (no reference counterpart; used by bench.py) ---------- */
 
 /* Enable (on != 0: counters reset) or disable (counters kept, readable) the

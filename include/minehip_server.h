@@ -56,10 +56,34 @@ typedef struct mh_sched mh_sched;
 mh_sched *mh_sched_create(const mh_sched_opts *opts);
 void mh_sched_destroy(mh_sched *s);
 
+/* Queueing.  A miner holds a FIFO of up to `depth` outstanding chunks, so that the small Requests
+ * of many clients reach it together and run as one fused batch (mh_miner_handle_batch).  A miner
+ * with q chunks out may be handed another iff q == 0, or q < depth and the nonces it holds are
+ * fewer than its budget: rate x queue_ns (init_chunk before the first rate sample).  The new
+ * chunk is sized as above and is not cut to the budget, so a chunk of a large job (rate x
+ * target_ns) fills the budget alone: large jobs are scheduled as at depth 1, small ones stack up.
+ * (The last chunks of a large job are the exception: the fair-share cap cuts them smaller than the
+ * budget, so several of them may queue on one miner, handed out fewest-first.)
+ * A Result carries no id: it completes the miner's oldest chunk (LSP delivers in order and a
+ * miner answers in arrival order).  With depth > 1 a Result is accepted only if its nonce lies in
+ * that chunk and Hash(job's Data, nonce) == hash, computed on the host; see mh_sched_result. */
+#define MH_SCHED_MAX_DEPTH 64 /* = the most payloads minehip-miner takes for one batch */
+typedef struct mh_sched_queue_opts {
+    uint32_t depth, reserved; /* most chunks one miner holds at once, 1..MH_SCHED_MAX_DEPTH; default 1 */
+    uint64_t queue_ns;        /* work one miner may hold, as time at its measured rate; 0 = target_ns */
+} mh_sched_queue_opts;
+
+/* depth 1, queue_ns 0. */
+void mh_sched_default_queue_opts(mh_sched_queue_opts *q);
+
+/* mh_sched_create with queue options; NULL q = defaults, which is mh_sched_create itself.  NULL
+ * (MH_EINVAL) also for depth 0 or above MH_SCHED_MAX_DEPTH, or reserved != 0. */
+mh_sched *mh_sched_create_ex(const mh_sched_opts *opts, const mh_sched_queue_opts *q);
+
 /* A miner joined (message.go:47 Join).  MH_EINVAL if the id is already known. */
 int mh_sched_add_miner(mh_sched *s, int64_t miner);
 
-/* A miner was lost: its outstanding chunk goes back to the front of its job.
+/* A miner was lost: every chunk it holds goes back to the front of its job, the oldest first.
  * MH_EINVAL if the id is unknown. */
 int mh_sched_remove_miner(mh_sched *s, int64_t miner);
 
@@ -78,11 +102,16 @@ typedef struct mh_assignment {
     size_t msg_len;        /* the job's Data: mh_sched_job_msg */
 } mh_assignment;
 
-/* Hand one chunk to an idle miner: `miner` = a specific miner, or -1 for
- * any idle one (miners in join order; jobs served round-robin in submission
- * order).  Returns 1 and fills *out, or 0 when no idle miner / no pending
- * chunk. */
+/* Hand one chunk to a miner that may take one (idle; with depth > 1 see "Queueing" above):
+ * `miner` = a specific miner, or -1 for the eligible miner with the fewest chunks out (ties in
+ * join order, so every miner gets its first chunk before any gets a second; jobs served
+ * round-robin in submission order).  Returns 1 and fills *out, or 0 when no eligible miner / no
+ * pending chunk. */
 int mh_sched_next(mh_sched *s, int64_t miner, uint64_t now_ns, mh_assignment *out);
+
+/* Host only: the chunks `miner` holds, oldest first, into out[0..cap); returns their count, or
+ * cap + 1 when there are more than cap (out holds the first cap).  MH_EINVAL if the id is unknown. */
+int64_t mh_sched_miner_queue(mh_sched *s, int64_t miner, mh_assignment *out, int64_t cap);
 
 /* Copy job `job`'s Data into buf (cap bytes); *len receives its size. */
 int mh_sched_job_msg(mh_sched *s, int64_t job, uint8_t *buf, size_t cap, size_t *len);
@@ -93,9 +122,13 @@ typedef struct mh_completion {
     uint64_t hash, nonce;
 } mh_completion;
 
-/* A miner's Result for its outstanding chunk.  Returns 1 when that finished
+/* A miner's Result for its oldest outstanding chunk.  Returns 1 when that finished
  * its job (*out filled), 0 otherwise.  MH_EINVAL: the miner has no chunk out;
- * MH_ERANGE: nonce outside the chunk (the chunk is requeued, the miner idle). */
+ * MH_ERANGE (depth 1): nonce outside the chunk (the chunk is requeued, the miner idle).
+ * MH_EREJECTED (depth > 1): nonce outside the chunk, or hash != Hash(job's Data, nonce) -- the
+ * miner skipped or reordered an answer, so its later Results would be credited to the wrong
+ * chunks: it is removed as if lost (every chunk it holds is requeued) and the caller should close
+ * its connection. */
 int mh_sched_result(mh_sched *s, int64_t miner, uint64_t hash, uint64_t nonce, uint64_t now_ns,
                     mh_completion *out);
 
@@ -114,6 +147,8 @@ int mh_sched_stats_read(mh_sched *s, mh_sched_stats *out);
 typedef struct mh_server mh_server;
 
 mh_server *mh_server_create(const mh_sched_opts *opts);
+/* The same over mh_sched_create_ex's scheduler (NULL q = depth 1). */
+mh_server *mh_server_create_ex(const mh_sched_opts *opts, const mh_sched_queue_opts *q);
 void mh_server_destroy(mh_server *v);
 
 /* lsp.Server.Read returned (conn, payload, nil).  Join registers a miner,
@@ -123,7 +158,9 @@ void mh_server_destroy(mh_server *v);
  * a client Request that can never be answered (Lower > Upper, Data longer
  * than MH_MAX_MSG_LEN): nothing is queued, and the caller should close that
  * connection (lsp.Server.CloseConn) so the client sees it end instead of
- * waiting forever for a Result. */
+ * waiting forever for a Result.  MH_EREJECTED also for a miner's Result that
+ * mh_sched_result refused at depth > 1: the miner is gone from the server and
+ * its chunks are handed out again; close that connection too. */
 int mh_server_read(mh_server *v, int64_t conn, const char *payload, size_t len, uint64_t now_ns);
 
 /* lsp.Server.Read returned (conn, nil, err): the connection is lost. */
