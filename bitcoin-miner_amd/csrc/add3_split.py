@@ -13,7 +13,7 @@ the price of one more instruction.  The chip runs this kernel at its power limit
 quad-cycles per nonce come back partly as a lower clock; measured with the in-kernel clock probe,
 every 4th add3 split ran 5% fewer quad-cycles per nonce at a 4% lower clock.
 
-like_split.s (the first-hit, hits and batch builds, -DMH_FIRST / -DMH_HITS / -DMH_BATCH: the product's split assembly): the count of a kernel
+like_split.s (the first-hit, hits and batch builds, -DMH_FIRST [-DMH_STOP] / -DMH_HITS / -DMH_BATCH: the product's split assembly): the count of a kernel
 whose <J, MODE> that file also holds starts at the phase 0..K-1 at which its per-nonce loop keeps as
 many v_add3 as that kernel's loop there.  The two builds' loops hold the same instructions, but the
 code before them differs by a few add3, which would shift "every K-th" by one inside the loop: one
@@ -51,8 +51,8 @@ def split_line(m):
 # entry label of a fast kernel: fast_search<J, MODE>, first_scan<J, MODE> of the -DMH_FIRST build
 # or hits_scan<J, MODE> of the -DMH_HITS build or batch_fast<J, MODE> of the -DMH_BATCH builds or
 # batch_first<J, MODE> of the -DMH_BATCH -DMH_FIRST build or batch_hits<J, MODE> of the -DMH_BATCH
-# -DMH_HITS build
-KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits)\S*:")
+# -DMH_HITS build or stop_scan<J, MODE> of the -DMH_FIRST -DMH_STOP build
+KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits|9stop_scan)\S*:")
 
 
 def split(text, k, pattern=None, phase=None):

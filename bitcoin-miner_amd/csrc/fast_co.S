@@ -11,7 +11,10 @@
    kernels of mh_search_first_batch_ex (-DMH_BATCH -DMH_FIRST,
    build/fast_batch_first.hsaco), loaded likewise, and the hits batch kernels
    of mh_search_hits_batch_ex (-DMH_BATCH -DMH_HITS,
-   build/fast_batch_hits.hsaco), loaded likewise. */
+   build/fast_batch_hits.hsaco), loaded likewise, and the stopping first-hit
+   kernels of mh_search_first_ex (-DMH_FIRST -DMH_STOP,
+   build/fast_first_stop.hsaco), loaded per device by the first such search
+   that asks for MH_FIRST_STOP_RUNNING. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -61,4 +64,12 @@ mh_batch_hits_co_begin:
     .globl mh_batch_hits_co_end
 mh_batch_hits_co_end:
     .size mh_batch_hits_co_begin, mh_batch_hits_co_end - mh_batch_hits_co_begin
+    .p2align 12
+    .globl mh_first_stop_co_begin
+    .type mh_first_stop_co_begin, @object
+mh_first_stop_co_begin:
+    .incbin "fast_first_stop.hsaco"
+    .globl mh_first_stop_co_end
+mh_first_stop_co_end:
+    .size mh_first_stop_co_begin, mh_first_stop_co_end - mh_first_stop_co_begin
     .section .note.GNU-stack,"",@progbits

@@ -31,6 +31,10 @@
 // -DMH_BATCH -DMH_HITS builds batch_hits<J, MODE> (build/fast_batch_hits.hsaco, through the same
 // passes): batch_fast's table and grid around the hits chunk body, a sixth embedded
 // code object that mh_search_hits_batch_ex loads; likewise.
+// -DMH_FIRST -DMH_STOP builds stop_scan<J, MODE> (build/fast_first_stop.hsaco, through the same
+// passes): first_scan whose waves publish a hit when they find it and leave a running
+// chunk once it lies wholly above a published hit, a seventh embedded code object that
+// mh_search_first_ex(MH_FIRST_STOP_RUNNING) loads; likewise (everything of it sits under MH_STOP).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -191,6 +195,10 @@ struct FirstKernArgs {
 __device__ __forceinline__ const FirstArgs& first_args(const FastArgs& a) {
     return ((const FirstKernArgs*)&a)->f;
 }
+#ifdef MH_STOP
+template <int MODE>
+__device__ __forceinline__ uint64_t chunk_floor(const FastArgs& a, uint32_t blk);  // below, beside claim_first
+#endif
 #endif
 #ifdef MH_HITS
 // The parameters of hits_scan<J, MODE> (below) as the kernarg segment holds them.
@@ -323,8 +331,36 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
     const uint32_t xor0 = mh_dev_hash_xor[0], xor1 = mh_dev_hash_xor[1];  // the hash-XOR hook, before the mask
 #endif
 
+#ifdef MH_STOP
+    uint32_t g = 0;  // after the loop: the groups this wave hashed
+    for (; g < a.n_groups; ++g) {
+#else
     for (uint32_t g = 0; g < a.n_groups; ++g) {
+#endif
         // ---- per group of 10 nonces --------------------------------------
+#ifdef MH_FIRST
+#ifdef MH_STOP
+        // One poll of the search's word per group, outside the per-nonce loop: once every nonce of
+        // this chunk lies above a published hit (chunk_floor, attained, so exact) the wave leaves
+        // the loop for the chunk's end -- block_min, its barriers and the chunk's Partial, which then
+        // carries a key that loses to the published hit's in every merge.  The word
+        // is written by other workgroups' atomics, so it is read as claim_first reads it: a relaxed
+        // agent-scope load (a vector load past this CU's L1, never the scalar cache), made
+        // wave-uniform.  A poll, never a wait: a stale value only stops later.  The kernel's
+        // arguments come through a pointer laundered here, so neither the word's address nor the
+        // floor is held across the per-nonce loop.
+        {
+            using KStop = __attribute__((address_space(4))) const FirstKernArgs;
+            KStop* ks = (KStop*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ks));
+            const FirstKernArgs& sk = *(const FirstKernArgs*)ks;
+            const uint64_t seen = __hip_atomic_load(sk.f.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t word = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(seen >> 32)) << 32) |
+                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)seen);
+            if (chunk_floor<MODE>(sk.a, blk) > word) break;
+        }
+#endif
+#endif
         // the L-1 digits of g: wave-uniform, so this is SALU work.  Into word J (cj) or word
         // J - 1 (cjm; the Early layouts put every group digit in word J)
         uint32_t cj = 0u, cjm = 0u, gq = g;
@@ -514,6 +550,16 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                         cn = spread(wave_u0 + l, a.hole, a.hole_w) * a.u_mul + spread(g, a.g_hole, 1u) * a.g_mul +
                              i * a.i_mul;
                     if ((wbh0 | wbh1) != 0u || cn < wbn) {  // the wave's first hit, or a smaller nonce than its hit's
+#ifdef MH_STOP
+                        // published when found, not only at the chunk's end: one lane lowers the
+                        // search's word (the chunk end's vector atomic), only when the wave's best
+                        // hit changes.  The empty statement keeps the lane branch's join a block of
+                        // its own: folded into the join that merges the wave's best, it made that
+                        // best lane-varying (VGPRs, and VALU compares in the per-nonce loop).
+                        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+                            atomicMin(first_args(a).first, (unsigned long long)cn);
+                        asm volatile("");
+#endif
                         wbh0 = 0u;
                         wbh1 = 0u;
                         wbn = cn;
@@ -561,6 +607,12 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
 #undef MH_R
 
 #ifdef MH_FIRST
+#ifdef MH_STOP
+    // scanned: what this wave hashed -- its valid lanes x the groups it ran x 10 -- one atomic per wave
+    // (claim_first adds nothing in this build)
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+        atomicAdd(first_args(a).scanned, (unsigned long long)__builtin_popcountll(valid_mask) * g * 10ull);
+#endif
     if (wbh0 == (uint32_t)(first_args(a).target >> 32) && wbh1 == 0u) wbh0 = 0u;  // lim -> k0
 #endif
     uint64_t hash = ((uint64_t)wbh0 << 32) | wbh1;  // wave-uniform: the wave step of block_min
@@ -778,6 +830,9 @@ __device__ __forceinline__ uint32_t claim_first(Partial* __restrict__ partials) 
             b = a.counter ? atomicAdd(a.counter, 1u) : blockIdx.x;
             if (b >= a.n_chunks) break;
             const uint64_t seen = __hip_atomic_load(f.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef MH_STOP
+            if (chunk_floor<MODE>(a, b) <= seen) break;  // run it: its waves count what they hash (fast_chunk)
+#else
             if (chunk_floor<MODE>(a, b) <= seen) {
                 // this chunk will be run: its valid nonces count as scanned
                 const uint32_t left = a.n_runs - b * (uint32_t)kBlockThreads;  // b < n_chunks: >= 1
@@ -785,6 +840,7 @@ __device__ __forceinline__ uint32_t claim_first(Partial* __restrict__ partials) 
                 atomicAdd(f.scanned, (unsigned long long)lanes * a.n_groups * 10ull);
                 break;
             }
+#endif
             uint64_t ones = ~0ull;
             asm volatile("" : "+v"(ones));  // made here: hoisted, the sentinel held 4 VGPRs across the chunk
             partials[b] = Partial{ones, ones};
@@ -802,10 +858,17 @@ __device__ __forceinline__ uint32_t claim_first(Partial* __restrict__ partials) 
 }
 
 // fast_search's loop over claim_first: every chunk the loop sees is run.
+// (-DMH_STOP: the same loop as stop_scan<J, MODE>, whose chunk body may leave a chunk early.)
 template <int J, int MODE>
+#ifdef MH_STOP
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void stop_scan(const FastArgs a,
+                                                                         Partial* __restrict__ partials,
+                                                                         const FirstArgs) {
+#else
 __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void first_scan(const FastArgs a,
                                                                           Partial* __restrict__ partials,
                                                                           const FirstArgs) {
+#endif
     using KArgs = __attribute__((address_space(4))) const FirstKernArgs;
     KArgs* const kp = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     uint32_t blk = claim_first<MODE>(partials);
@@ -884,8 +947,13 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 #define MH_INST(j, m) template __global__ void fast_search<j, m>(const FastArgs, Partial* __restrict__);
 #endif
 #else
+#ifdef MH_STOP
+#define MH_INST(j, m) \
+    template __global__ void stop_scan<j, m>(const FastArgs, Partial* __restrict__, const FirstArgs);
+#else
 #define MH_INST(j, m) \
     template __global__ void first_scan<j, m>(const FastArgs, Partial* __restrict__, const FirstArgs);
+#endif
 #endif
 #endif  // MH_BATCH
 MH_FAST_KERNELS(MH_INST)  // layout.hpp: the one list of instantiated layouts

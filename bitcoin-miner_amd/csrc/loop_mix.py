@@ -64,6 +64,7 @@ HITS = re.compile(r"^_ZN2mh9hits_scanILi(\d+)ELi(\d+)EE")  # the -DMH_HITS build
 BATCH = re.compile(r"^_ZN2mh10batch_fastILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH builds' kernels (build/fast_batch*_prio.s)
 # the -DMH_BATCH -DMH_FIRST build's kernels (build/fast_batch_first_prio.s); with whole=True: they exit early
 BATCH_FIRST = re.compile(r"^_ZN2mh11batch_firstILi(\d+)ELi(\d+)EE")
+STOP = re.compile(r"^_ZN2mh9stop_scanILi(\d+)ELi(\d+)EE")  # the -DMH_FIRST -DMH_STOP build's kernels (build/fast_first_stop_prio.s)
 BATCH_HITS = re.compile(r"^_ZN2mh10batch_hitsILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH -DMH_HITS build's kernels (build/fast_batch_hits_prio.s)
 
 

@@ -43,7 +43,7 @@ hipError_t launch_hash_batch(const GenArgs& a, const uint64_t* d_nonces, uint64_
                              hipStream_t s);
 hipError_t launch_merge(const Partial* partials, uint32_t n, Partial* best, hipStream_t s);
 hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partial* partials, const FirstArgs& f,
-                             hipStream_t s);
+                             bool stop, hipStream_t s);
 hipError_t launch_generic_scan_first(const GenArgs& a, Partial* partials, uint32_t blocks, const FirstArgs& f,
                                      hipStream_t s);
 hipError_t launch_finish_first(const GenArgs& a, const Partial* best, const unsigned long long* scanned, uint64_t* out,
@@ -172,6 +172,7 @@ struct DevCtx {
     uint64_t* d_first = nullptr;  // [0] smallest qualifying nonce so far, [1] nonces scanned, [2..4] the result
     uint64_t* h_first = nullptr;  // pinned: hash, nonce, scanned
     const mh::FirstArgs* first = nullptr;  // set while an mh_search_first enqueues its pieces
+    bool first_stop = false;               // ... of mh_search_first_ex(MH_FIRST_STOP_RUNNING): stop_scan for first_scan
     // every hit (mh_search_hits), allocated by the first such call
     mh::Hit* d_hits = nullptr;      // MH_HITS_MAX_CAP entries
     uint64_t* d_hcursor = nullptr;  // hits of the scan in flight
@@ -424,7 +425,7 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
     }
     if (c->first) {  // mh_search_first: the first-hit kernels over the same pieces
         if (p.kind == 0)
-            MH_HIP(mh::launch_fast_first(c->dev, p.J, p.mode, fa, out, *c->first, s));
+            MH_HIP(mh::launch_fast_first(c->dev, p.J, p.mode, fa, out, *c->first, c->first_stop, s));
         else
             MH_HIP(mh::launch_generic_scan_first(ga, out, blocks, *c->first, s));
     } else if (c->hits) {  // mh_search_hits: the hits kernels over the same pieces
@@ -576,7 +577,10 @@ int search_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, 
 // first-hit kernels (first_scan<J, MODE>, generic_scan_first; layout.hpp FirstArgs), then
 // finish_first on the main stream and one 24-byte copy-back with the one synchronise.  The word
 // the kernels skip later chunks by and the scanned count are reset beside the running minimum.
-int search_first_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, mh_first* out) {
+// flags (mh_search_first_ex, checked by the caller): MH_FIRST_STOP_RUNNING launches stop_scan<J, MODE>
+// in place of first_scan<J, MODE>; nothing else differs.
+int search_first_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, uint32_t flags,
+                      mh_first* out) {
     DevCtx* c;
     int rc = get_ctx(dev, &c);
     if (rc) return rc;
@@ -611,11 +615,13 @@ int search_first_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t u
     int err = MH_OK;
     c->poff = 0;
     c->first = &fargs;
+    c->first_stop = (flags & MH_FIRST_STOP_RUNNING) != 0;
     mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
         err = enqueue_piece(c, p, opt, split);
         return err == MH_OK;
     });
     c->first = nullptr;
+    c->first_stop = false;
     if (!err) err = flush_partials(c, split);
     if (err) {
         for (auto ps : c->ps)
@@ -1796,7 +1802,13 @@ int mh_search(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t 
 
 int mh_search_first(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
                     mh_first* out) {
+    return mh_search_first_ex(dev, msg, len, lower, upper, target, 0u, out);
+}
+
+int mh_search_first_ex(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                       uint32_t flags, mh_first* out) {
     g_err.clear();
+    if (flags & ~MH_FIRST_STOP_RUNNING) return fail(MH_EINVAL, "unknown flag bit");
     if (!out) return fail(MH_EINVAL, "NULL output pointer");
     int rc = check_common(msg, len);
     if (rc) return rc;
@@ -1809,7 +1821,7 @@ int mh_search_first(int dev, const uint8_t* msg, size_t len, uint64_t lower, uin
 #endif
     mh::Prefix pre;
     mh::absorb_prefix(msg, len, &pre);
-    return search_first_impl(dev, pre, lower, upper, target, out);
+    return search_first_impl(dev, pre, lower, upper, target, flags, out);
 }
 
 int mh_search_hits(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
@@ -2014,7 +2026,7 @@ int mh_search_first_batch(int dev, const mh_first_request* reqs, size_t n, mh_fi
         if (it.kind != 1) continue;
         const mh::BatchRequest& r = valid[it.idx];
         mh_first f;
-        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, &f);
+        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, 0u, &f);
         if (rc) return rc;
         put_first_result(&out[r.id], f.hash, f.nonce, f.scanned, reqs[r.id].target);
     }
@@ -2055,7 +2067,7 @@ int mh_search_first_batch_ex(int dev, const mh_first_request* reqs, size_t n, ui
         if (p.kind != 1) continue;
         const mh::BatchRequest& r = valid[p.idx];
         mh_first f;
-        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, &f);
+        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, 0u, &f);
         if (rc) return rc;
         put_first_result(&out[r.id], f.hash, f.nonce, f.scanned, reqs[r.id].target);
     }

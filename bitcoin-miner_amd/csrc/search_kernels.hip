@@ -23,6 +23,10 @@
 //   first_scan<J, MODE>   (fast_search.hip, -DMH_FIRST) fast_search for mh_search_first: the
 //                         smallest nonce whose hash is <= a target, later chunks skipped; a
 //                         second embedded code object, loaded by the first such search.
+//   stop_scan<J, MODE>    (fast_search.hip, -DMH_FIRST -DMH_STOP) first_scan whose waves publish a hit
+//                         when found and leave a running chunk that lies wholly above a published
+//                         hit, for mh_search_first_ex(MH_FIRST_STOP_RUNNING); a seventh embedded
+//                         code object, loaded by the first such search.
 //   generic_scan_first    generic_scan for mh_search_first.
 //   finish_first          one thread: the winning key back into its hash, the result out.
 //   hits_scan<J, MODE>    (fast_search.hip, -DMH_HITS) fast_search for mh_search_hits: every nonce
@@ -86,6 +90,8 @@ extern "C" const unsigned char mh_hits_co_begin[];
 extern "C" const unsigned char mh_batch_co_begin[];
 // the same source built with -DMH_BATCH -DMH_FIRST: batch_first<J, MODE>, the fused fast pieces of mh_search_first_batch_ex
 extern "C" const unsigned char mh_batch_first_co_begin[];
+// the same source built with -DMH_FIRST -DMH_STOP: stop_scan<J, MODE>, the fast kernels of mh_search_first_ex(MH_FIRST_STOP_RUNNING)
+extern "C" const unsigned char mh_first_stop_co_begin[];
 // the same source built with -DMH_BATCH -DMH_HITS: batch_hits<J, MODE>, the fused fast pieces of mh_search_hits_batch_ex
 extern "C" const unsigned char mh_batch_hits_co_begin[];
 
@@ -779,7 +785,10 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // marker is mh_fast_batch_first_items at sizeof(BatchFirstItem)
 // or kFastBatchHits, batch_hits<J, MODE> of the sixth (":batch_hits"; no hook replaces it), whose
 // marker is mh_fast_batch_hits_items at sizeof(BatchHitsItem)
-enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4, kFastBatchHits = 5 };
+// or kFastFirstStop, stop_scan<J, MODE> of the seventh (":first_stop"; no hook replaces it): first_scan's
+// parameters and marker
+enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4, kFastBatchHits = 5,
+                   kFastFirstStop = 6 };
 #ifdef MH_DEV_HOOKS
 std::string batch_module_path() {
     const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
@@ -791,20 +800,21 @@ std::string batch_module_path() { return ":batch"; }
 hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue_ok = nullptr,
                          FastVariant variant = kFastProduct) {
     const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
-    const bool bfirst = variant == kFastBatchFirst, bhits = variant == kFastBatchHits;
+    const bool bfirst = variant == kFastBatchFirst, bhits = variant == kFastBatchHits, fstop = variant == kFastFirstStop;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
-    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path()
+    const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : batch ? batch_module_path()
                              : bfirst ? ":batch_first" : bhits ? ":batch_hits" : (co && *co) ? co : "";
 #else
-    const std::string path = first ? ":first" : hits ? ":hits" : batch ? batch_module_path() : bfirst ? ":batch_first"
-                             : bhits ? ":batch_hits" : "";
+    const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : batch ? batch_module_path()
+                             : bfirst ? ":batch_first" : bhits ? ":batch_hits" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
     if (it == g_mods.end()) {
         hipModule_t m;
         const hipError_t e = first          ? hipModuleLoadData(&m, mh_first_co_begin)
+                             : fstop        ? hipModuleLoadData(&m, mh_first_stop_co_begin)
                              : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
                              : path == ":batch" ? hipModuleLoadData(&m, mh_batch_co_begin)
                              : bfirst       ? hipModuleLoadData(&m, mh_batch_first_co_begin)
@@ -849,6 +859,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                  bfirst ? "_ZN2mh11batch_firstILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
                  : bhits ? "_ZN2mh10batch_hitsILi%dELi%dEEEvPKNS_13BatchHitsItemEPKjPNS_7PartialE"
                  : first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
+                 : fstop ? "_ZN2mh9stop_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
                  : batch ? "_ZN2mh10batch_fastILi%dELi%dEEEvPKNS_13BatchFastItemEPKjPNS_7PartialE"
                         : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
@@ -1006,10 +1017,12 @@ hipError_t launch_fast_variant(int dev, int J, int mode, const FastArgs& a, Part
 }  // namespace
 
 // mh_search_first: first_scan<J, mode> of the first-hit code object, f as the third kernel parameter.
+// stop: stop_scan<J, mode> of the stopping first-hit code object instead (mh_search_first_ex,
+// MH_FIRST_STOP_RUNNING), loaded on dev by the first such call.
 hipError_t launch_fast_first(int dev, int J, int mode, const FastArgs& a, Partial* partials, const FirstArgs& f,
-                             hipStream_t s) {
+                             bool stop, hipStream_t s) {
     FirstArgs fa = f;
-    return launch_fast_variant(dev, J, mode, a, partials, kFastFirst, &fa, s);
+    return launch_fast_variant(dev, J, mode, a, partials, stop ? kFastFirstStop : kFastFirst, &fa, s);
 }
 
 // mh_search_hits: hits_scan<J, mode> of the hits code object, h as the third kernel parameter.

@@ -38,7 +38,7 @@ from ._lib import MH_OK, MH_EINVAL, MH_ERANGE, MH_ETOOLONG, MH_ENODEV, MH_EHIP  
 from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
 from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
 from ._lib import mh_batch_piece, MH_BATCH_FUSE_FAST, MH_BATCH_FAST_MAX_NONCES  # noqa: F401
-from ._lib import mh_first_request, mh_first_result  # noqa: F401
+from ._lib import mh_first_request, mh_first_result, MH_FIRST_STOP_RUNNING  # noqa: F401
 from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP  # noqa: F401
 from ._lib import mh_hits_request, mh_hits_result, mh_hits_region  # noqa: F401
 
@@ -73,12 +73,17 @@ def search(msg, lower, upper, dev=0):
     return h.value, n.value
 
 
-def search_first(msg, lower, upper, target, dev=0):
+def search_first(msg, lower, upper, target, dev=0, stop_running=False):
     """(found, hash, nonce, scanned): the smallest nonce n of [lower, upper] with Hash(msg, n) <=
     target and its hash (found True), or search()'s (hash, nonce) when none qualifies (found
-    False); scanned is how many nonces of the range were hashed (mh_search_first)."""
+    False); scanned is how many nonces of the range were hashed (mh_search_first).
+    stop_running: mh_search_first_ex with MH_FIRST_STOP_RUNNING -- the same answer, from kernels that
+    also leave a chunk already running once it lies wholly above a published hit."""
     m = _b(msg)
     out = mh_first()
+    if stop_running:
+        _check(lib.mh_search_first_ex(dev, m, len(m), lower, upper, target, MH_FIRST_STOP_RUNNING, ctypes.byref(out)))
+        return bool(out.found), out.hash, out.nonce, out.scanned
     _check(lib.mh_search_first(dev, m, len(m), lower, upper, target, ctypes.byref(out)))
     return bool(out.found), out.hash, out.nonce, out.scanned
 

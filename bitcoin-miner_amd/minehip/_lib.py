@@ -30,6 +30,7 @@ MH_MAX_WORKERS = 256  # most devices one mh_search_multi / mh_multi_plan call ma
 MH_HITS_MAX_CAP = 1 << 20  # most entries one mh_search_hits call returns
 MH_BATCH_FUSE_FAST = 1     # mh_search_batch_ex / mh_batch_plan_ex flag
 MH_BATCH_FAST_MAX_NONCES = 10 ** 9  # most nonces of a request MH_BATCH_FUSE_FAST fuses
+MH_FIRST_STOP_RUNNING = 1  # mh_search_first_ex flag
 MH_SCHED_MAX_DEPTH = 64    # include/minehip_server.h: most chunks one miner may hold at once
 
 #: every symbol include/*.h declares
@@ -41,7 +42,7 @@ EXPORTS = (
     "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
     "mh_search_hits_batch", "mh_hits_batch_regions", "mh_search_batch_ex", "mh_batch_plan_ex",
     "mh_search_first_batch_ex", "mh_first_batch_order_ex", "mh_search_hits_batch_ex", "mh_hits_batch_regions_ex",
-    "mh_miner_handle_batch_ex",
+    "mh_miner_handle_batch_ex", "mh_search_first_ex",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -201,6 +202,7 @@ def _load():
     L.mh_multi_rates.argtypes = [intp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
     L.mh_search_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_result)]
     L.mh_search_first.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.POINTER(mh_first)]
+    L.mh_search_first_ex.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(mh_first)]
     L.mh_search_hits.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.POINTER(mh_hit), sz,
                                  ctypes.POINTER(mh_hits)]
     L.mh_search_first_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_first_request), sz,

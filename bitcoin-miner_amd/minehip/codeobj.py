@@ -34,6 +34,15 @@ def first_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def first_stop_code_object():
+    """The embedded code object of the stopping first-hit kernels (mh_search_first_ex with
+    MH_FIRST_STOP_RUNNING): stop_scan<J, MODE>, fast_search.hip built with -DMH_FIRST -DMH_STOP
+    (mh_first_stop_co_begin .. mh_first_stop_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_first_stop_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_first_stop_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def hits_code_object():
     """The embedded code object of the hits kernels (mh_search_hits): hits_scan<J, MODE>,
     fast_search.hip built with -DMH_HITS (mh_hits_co_begin .. mh_hits_co_end)."""
@@ -173,6 +182,11 @@ def fast_kernel_resources(co=None, name=r"_ZN2mh11fast_searchILi(\d+)ELi(\d+)E")
 def first_kernel_resources():
     """The same of the embedded first_scan<J, MODE> kernels."""
     return fast_kernel_resources(first_code_object(), r"_ZN2mh10first_scanILi(\d+)ELi(\d+)E")
+
+
+def first_stop_kernel_resources():
+    """The same of the embedded stop_scan<J, MODE> kernels."""
+    return fast_kernel_resources(first_stop_code_object(), r"_ZN2mh9stop_scanILi(\d+)ELi(\d+)E")
 
 
 def hits_kernel_resources():

@@ -172,6 +172,26 @@ typedef struct mh_first {
 int mh_search_first(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                     uint64_t target, mh_first *out);
 
+/* mh_search_first with flags.  flags == 0 is exactly mh_search_first; an unknown flag bit returns
+ * MH_EINVAL before any device is touched.  mh_search_first skips work that has not begun: a
+ * 256-run chunk that is already running when a hit becomes known runs to its end, and reports its
+ * own hit only there.  With MH_FIRST_STOP_RUNNING (the only flag) the fast kernels are
+ * stop_scan<J, MODE> (a code object of its own, loaded by the first call that asks for it): a wave
+ * publishes a hit when it finds it, and once per group of ten nonces -- outside the per-nonce loop,
+ * which stays the product's -- polls the published value and leaves its chunk when every nonce of
+ * the chunk lies above it.  Nothing waits on the value.
+ * found, hash and nonce are bit for bit mh_search_first's, whatever the plan, streams, queue mode
+ * or timing (the published value is always a qualifying nonce of the range, so an abandoned chunk
+ * holds only nonces above the answer; DESIGN.md section 3 has the argument).  scanned is still the
+ * nonces of the range actually hashed, counted on the device by the waves themselves:
+ * upper - lower + 1 when nothing qualifies, else within [nonce - lower + 1, upper - lower + 1].
+ * Errors and conventions are mh_search_first's.  Opt-in: DESIGN.md section 3 has what the poll
+ * costs a search without an early hit.  The batched forms do not take the flag.
+ * Additive in ABI 5 (no existing struct or function changes). */
+#define MH_FIRST_STOP_RUNNING 1u
+int mh_search_first_ex(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
+                       uint64_t target, uint32_t flags, mh_first *out);
+
 /* ---- batched first-hit search: many small proof-of-work questions at once ---- */
 
 typedef struct mh_first_request {

@@ -13,6 +13,17 @@ Required:
 The ratio of a hit case to its knew-where-to-stop scan is reported, not required.
 
     python tools/first_latency.py [--rounds 11] [--out profiles/first_search.json]
+
+--stop: mh_search_first_ex(MH_FIRST_STOP_RUNNING) against mh_search_first (flags 0, whose code
+objects are the ones from before the flag existed: the yardstick, on the same device in the same run).
+Per target 2^64 // 10^k, k in {4, 6, 8, 9}, and target 0 (nothing qualifies: the whole range, the
+poll's cost), alternating rounds of flags 0 and the flag; medians, interquartile ranges and the range
+of `scanned` on both sides.  Reported per row: whether the flag's median is below flags 0's by more
+than both interquartile ranges (k = 6 is the case the flag is for), and for target 0 whether it is
+slower by more than the flags-0 spread.  Nothing is required: the exit code is 0 once every answer
+matched.
+
+    python tools/first_latency.py --stop [--rounds 11] [--out profiles/first_stop_search.json]
 """
 import argparse
 import json
@@ -41,13 +52,60 @@ def timed(fn):
     return time.perf_counter() - t, r
 
 
+def stop_main(a):
+    """--stop: flags 0 against MH_FIRST_STOP_RUNNING, one process, alternating rounds."""
+    plain = lambda T: minehip.search_first(MSG, LO, HI, T)  # noqa: E731
+    stop = lambda T: minehip.search_first(MSG, LO, HI, T, stop_running=True)  # noqa: E731
+    rows = {"k%d" % k: 2 ** 64 // 10 ** k for k in KS}
+    rows["nohit"] = 0
+    want = {}
+    for name, T in rows.items():
+        for _ in range(2):  # warm: both code objects loaded, every kernel of the plan run
+            want[name] = plain(T)
+            got = stop(T)
+            assert got[:3] == want[name][:3], (name, got, want[name])
+    size = HI - LO + 1
+    t = {name: {"flags0": [], "stop": []} for name in rows}
+    sc = {name: {"flags0": [], "stop": []} for name in rows}
+    for _ in range(a.rounds):
+        for name, T in rows.items():
+            for side, fn in (("flags0", plain), ("stop", stop)):
+                dt, got = timed(lambda: fn(T))
+                assert got[:3] == want[name][:3], (name, side, got, want[name])   # the answer never depends on the timing
+                assert (got[2] - LO + 1 if got[0] else size) <= got[3] <= size, (name, side, got)
+                t[name][side].append(dt)
+                sc[name][side].append(got[3])
+    out = {"msg": MSG, "lower": LO, "upper": HI, "rounds": a.rounds, "rows": {}}
+    for name, T in rows.items():
+        f0, st = quartiles(t[name]["flags0"]), quartiles(t[name]["stop"])
+        found, h, n = want[name][:3]
+        row = {"target": T, "found": found, "hash": h, "nonce": n, "flags0": f0, "stop": st,
+               "flags0_scanned": [min(sc[name]["flags0"]), max(sc[name]["flags0"])],
+               "stop_scanned": [min(sc[name]["stop"]), max(sc[name]["stop"])],
+               "stop_over_flags0": round(st["median_ms"] / f0["median_ms"], 4),
+               "stop_below_flags0_by_more_than_both_iqr":
+                   f0["median_ms"] - st["median_ms"] > max(f0["iqr_ms"], st["iqr_ms"]),
+               "stop_above_flags0_by_more_than_flags0_iqr": st["median_ms"] - f0["median_ms"] > f0["iqr_ms"]}
+        out["rows"][name] = row
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=11)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "first_search.json"))
+    ap.add_argument("--stop", action="store_true", help="flags 0 against MH_FIRST_STOP_RUNNING (see above)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.rounds < 11:
         ap.error("--rounds: at least 11")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "first_stop_search.json" if a.stop else "first_search.json")
+    if a.stop:
+        return stop_main(a)
     full = lambda: minehip.search(MSG, LO, HI)  # noqa: E731
     nohit = lambda: minehip.search_first(MSG, LO, HI, 0)  # noqa: E731
     for _ in range(2):  # warm: both code objects loaded, every kernel of the plan run
