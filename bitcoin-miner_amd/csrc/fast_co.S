@@ -14,7 +14,10 @@
    build/fast_batch_hits.hsaco), loaded likewise, and the stopping first-hit
    kernels of mh_search_first_ex (-DMH_FIRST -DMH_STOP,
    build/fast_first_stop.hsaco), loaded per device by the first such search
-   that asks for MH_FIRST_STOP_RUNNING. */
+   that asks for MH_FIRST_STOP_RUNNING, and the stopping first-hit batch
+   kernels of mh_search_first_batch_stop (-DMH_BATCH -DMH_FIRST -DMH_STOP,
+   build/fast_batch_first_stop.hsaco), loaded per device by the first such
+   call that fuses a fast piece. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -72,4 +75,12 @@ mh_first_stop_co_begin:
     .globl mh_first_stop_co_end
 mh_first_stop_co_end:
     .size mh_first_stop_co_begin, mh_first_stop_co_end - mh_first_stop_co_begin
+    .p2align 12
+    .globl mh_batch_first_stop_co_begin
+    .type mh_batch_first_stop_co_begin, @object
+mh_batch_first_stop_co_begin:
+    .incbin "fast_batch_first_stop.hsaco"
+    .globl mh_batch_first_stop_co_end
+mh_batch_first_stop_co_end:
+    .size mh_batch_first_stop_co_begin, mh_batch_first_stop_co_end - mh_batch_first_stop_co_begin
     .section .note.GNU-stack,"",@progbits

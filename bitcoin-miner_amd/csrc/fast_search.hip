@@ -35,6 +35,10 @@
 // passes): first_scan whose waves publish a hit when they find it and leave a running
 // chunk once it lies wholly above a published hit, a seventh embedded code object that
 // mh_search_first_ex(MH_FIRST_STOP_RUNNING) loads; likewise (everything of it sits under MH_STOP).
+// -DMH_BATCH -DMH_FIRST -DMH_STOP builds batch_stop<J, MODE> (build/fast_batch_first_stop.hsaco, through
+// the same passes): batch_first's table, order and grid around stop_scan's chunk body,
+// which polls its request's word through the item, an eighth embedded code object that
+// mh_search_first_batch_stop loads; likewise (everything of it sits under MH_STOP).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -351,7 +355,16 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
         // floor is held across the per-nonce loop.
         {
             using KStop = __attribute__((address_space(4))) const FirstKernArgs;
+#ifdef MH_BATCH
+            // batch_stop: the kernarg segment holds the launch's four table pointers, so the word's
+            // address and the floor's terms come from the item `a` heads (layout.hpp BatchFirstItem:
+            // FastArgs and FirstArgs where FirstKernArgs has them), through a copy of the item's
+            // address laundered here for the same reason.  The word and the floor are this request's
+            // and this piece's.
+            KStop* ks = (KStop*)&a;
+#else
             KStop* ks = (KStop*)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
             asm volatile("" : "+s"(ks));
             const FirstKernArgs& sk = *(const FirstKernArgs*)ks;
             const uint64_t seen = __hip_atomic_load(sk.f.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -403,12 +416,35 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
             if (MH_G(t - 2)) v += ssig1(wg[t - 2]);
             if (MH_G(t)) wg[t] = v; else pg[t] = v;
         }
+#ifdef MH_STOP
+#ifdef MH_BATCH
+        // batch_stop: K[t] + W[t] of the group-level words the per-nonce rounds read, made opaque as
+        // kwr is.  Left to the compiler, the build with a store inside the group loop (the published
+        // hit) redoes one or two of these adds on every nonce in eight layouts, which batch_first's
+        // loops take hoisted.
+        uint32_t kwg[64];
+#pragma unroll
+        for (int t = 16; t < (BM == kModeTwo ? 64 : 63); ++t)
+            if (MH_G(t) && t > J) {
+                kwg[t] = K[t] + wg[t];
+                asm volatile("" : "+v"(kwg[t]));
+            }
+#endif
+#endif
         // round J-1 reads the group-level word J-1 (Early: it is run-level, done above)
         uint32_t ga = ra, gb = rb, gc = rc, gd = rd, ge = re, gf = rf, gG = rg, gh = rh;
         if constexpr (!EARLY && J > 0) round_kw(ga, gb, gc, gd, ge, gf, gG, gh, K[J - 1] + wg[J - 1]);
         // round J: every input but W[J]'s last digit is known here
         const uint32_t t1J = (gh + (K[J] + wJ)) + bsig1(ge) + ch(ge, gf, gG);
         const uint32_t t2J = bsig0(ga) + maj(ga, gb, gc);
+#ifdef MH_STOP
+#ifdef MH_BATCH
+        // ... and round J's two outputs without the digit: A = (t1J + t2J) + inc and
+        // E = (gd + t1J) + inc are two adds per nonce where t1 = t1J + inc, A = t1 + t2J, E = gd + t1
+        // are three, from two group-level registers instead of three
+        const uint32_t aJ = t1J + t2J, eJ = gd + t1J;
+#endif
+#endif
 
         for (uint32_t i = 0; i < 10u; ++i) {
             // ---- per nonce ------------------------------------------------
@@ -429,15 +465,35 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 if (MH_N(t - 2)) v += (t - 2 == J) ? (s1wJ ^ s1inc) : ssig1(x[t - 2]);
                 x[t] = v;
             };
+#ifdef MH_STOP
+#ifdef MH_BATCH
+            uint32_t A = aJ + inc, B = ga, C = gb, D = gc, E = eJ + inc, F = ge, G = gf, H = gG;
+#else
             const uint32_t t1 = t1J + inc;
             uint32_t A = t1 + t2J, B = ga, C = gb, D = gc, E = gd + t1, F = ge, G = gf, H = gG;
+#endif
+#else
+            const uint32_t t1 = t1J + inc;
+            uint32_t A = t1 + t2J, B = ga, C = gb, D = gc, E = gd + t1, F = ge, G = gf, H = gG;
+#endif
             uint32_t h0, a63;
             if constexpr (BM != kModeTwo) {
 #pragma unroll
                 for (int t = J + 1; t < 63; ++t) {
                     sched(t);
+#ifdef MH_STOP
+#ifdef MH_BATCH
+                    round_kw(A, B, C, D, E, F, G, H,
+                             (t >= 16 && MH_R(t)) ? kwr[t] : (t >= 16 && MH_G(t)) ? kwg[t]
+                                                  : K[t] + (MH_N(t) ? x[t] : wr[t]));
+#else
                     round_kw(A, B, C, D, E, F, G, H,
                              (t >= 16 && MH_R(t)) ? kwr[t] : K[t] + (MH_N(t) ? x[t] : (MH_G(t) ? wg[t] : wr[t])));
+#endif
+#else
+                    round_kw(A, B, C, D, E, F, G, H,
+                             (t >= 16 && MH_R(t)) ? kwr[t] : K[t] + (MH_N(t) ? x[t] : (MH_G(t) ? wg[t] : wr[t])));
+#endif
                 }
                 sched(63);
                 a63 = A;
@@ -448,8 +504,19 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 for (int t = 16; t < 64; ++t) sched(t);
 #pragma unroll
                 for (int t = J + 1; t < 64; ++t)
+#ifdef MH_STOP
+#ifdef MH_BATCH
+                    round_kw(A, B, C, D, E, F, G, H,
+                             (t >= 16 && MH_R(t)) ? kwr[t] : (t >= 16 && MH_G(t)) ? kwg[t]
+                                                  : K[t] + (MH_N(t) ? x[t] : wr[t]));
+#else
                     round_kw(A, B, C, D, E, F, G, H,
                              (t >= 16 && MH_R(t)) ? kwr[t] : K[t] + (MH_N(t) ? x[t] : (MH_G(t) ? wg[t] : wr[t])));
+#endif
+#else
+                    round_kw(A, B, C, D, E, F, G, H,
+                             (t >= 16 && MH_R(t)) ? kwr[t] : K[t] + (MH_N(t) ? x[t] : (MH_G(t) ? wg[t] : wr[t])));
+#endif
                 const uint32_t s2[8] = {st[0] + A, st[1] + B, st[2] + C, st[3] + D,
                                         st[4] + E, st[5] + F, st[6] + G, st[7] + H};
                 sha256_block_kw_last(s2, a.kw1, h0, a63);  // block 1: padding + length only
@@ -676,11 +743,21 @@ __device__ __forceinline__ uint64_t chunk_floor(const FastArgs& a, uint32_t blk)
 static_assert(__builtin_offsetof(BatchFirstItem, f) == __builtin_offsetof(FirstKernArgs, f) &&
                   __builtin_offsetof(BatchFirstItem, args) == 0,
               "first_args finds an item's FirstArgs where first_scan's kernarg segment holds them");
+#ifdef MH_STOP
+// (-DMH_STOP: the same wrapper as batch_stop<J, MODE>, whose chunk body may leave a chunk early; a
+// chunk that is run adds nothing to scanned here, its waves count what they hash, fast_chunk.)
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_stop(const BatchFirstItem* __restrict__ items,
+                                                                          const uint32_t* __restrict__ chunk_item,
+                                                                          const uint32_t* __restrict__ order,
+                                                                          Partial* __restrict__ partials) {
+#else
 template <int J, int MODE>
 __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_first(const BatchFirstItem* __restrict__ items,
                                                                            const uint32_t* __restrict__ chunk_item,
                                                                            const uint32_t* __restrict__ order,
                                                                            Partial* __restrict__ partials) {
+#endif
     using KItem = __attribute__((address_space(4))) const BatchFirstItem;
     __shared__ uint32_t s_skip;
     const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[blockIdx.x]);
@@ -699,10 +776,12 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_first
             partials[slot0 + blk] = Partial{ones, ones};
             skip = 1u;
         } else {
+#ifndef MH_STOP
             // this chunk will be run: its valid nonces count as scanned
             const uint32_t left = a.n_runs - blk * (uint32_t)kBlockThreads;  // blk < n_chunks: >= 1
             const uint32_t lanes = left < (uint32_t)kBlockThreads ? left : (uint32_t)kBlockThreads;
             atomicAdd(f.scanned, (unsigned long long)lanes * a.n_groups * 10ull);
+#endif
         }
         s_skip = skip;
     }
@@ -893,7 +972,12 @@ extern "C" {
 #ifdef MH_FIRST
 // Marker of the first-hit batch code object instead: its kernels read BatchFirstItems of this size
 // (the library launches batch_first only from a code object that carries it, search_kernels.hip).
+#ifdef MH_STOP
+// (of the stopping first-hit batch code object: batch_stop is launched only from one that carries this)
+__device__ __attribute__((used)) uint8_t mh_fast_batch_stop_items[sizeof(BatchFirstItem)];
+#else
 __device__ __attribute__((used)) uint8_t mh_fast_batch_first_items[sizeof(BatchFirstItem)];
+#endif
 #else
 #ifdef MH_HITS
 // Marker of the hits batch code object instead: its kernels read BatchHitsItems of this size (the
@@ -924,9 +1008,15 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 // in word J + 1 (plan.cpp: nonce_cost(J) < nonce_cost(J + 1)).
 #ifdef MH_BATCH
 #ifdef MH_FIRST
+#ifdef MH_STOP
+#define MH_INST(j, m) \
+    template __global__ void batch_stop<j, m>(const BatchFirstItem* __restrict__, const uint32_t* __restrict__, \
+                                              const uint32_t* __restrict__, Partial* __restrict__);
+#else
 #define MH_INST(j, m) \
     template __global__ void batch_first<j, m>(const BatchFirstItem* __restrict__, const uint32_t* __restrict__, \
                                                const uint32_t* __restrict__, Partial* __restrict__);
+#endif
 #else
 #ifdef MH_HITS
 #define MH_INST(j, m) \

@@ -65,6 +65,8 @@ BATCH = re.compile(r"^_ZN2mh10batch_fastILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH b
 # the -DMH_BATCH -DMH_FIRST build's kernels (build/fast_batch_first_prio.s); with whole=True: they exit early
 BATCH_FIRST = re.compile(r"^_ZN2mh11batch_firstILi(\d+)ELi(\d+)EE")
 STOP = re.compile(r"^_ZN2mh9stop_scanILi(\d+)ELi(\d+)EE")  # the -DMH_FIRST -DMH_STOP build's kernels (build/fast_first_stop_prio.s)
+# the -DMH_BATCH -DMH_FIRST -DMH_STOP build's kernels (build/fast_batch_first_stop_prio.s); whole=True, as batch_first's
+BATCH_STOP = re.compile(r"^_ZN2mh10batch_stopILi(\d+)ELi(\d+)EE")
 BATCH_HITS = re.compile(r"^_ZN2mh10batch_hitsILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH -DMH_HITS build's kernels (build/fast_batch_hits_prio.s)
 
 

@@ -77,6 +77,8 @@ hipError_t launch_merge_segments_first_ex(const Partial* partials, const uint32_
                                           hipStream_t s);
 hipError_t launch_batch_first(int dev, int J, int mode, const BatchFirstItem* items, const uint32_t* chunk_item,
                               const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s);
+hipError_t launch_batch_stop(int dev, int J, int mode, const BatchFirstItem* items, const uint32_t* chunk_item,
+                             const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s);
 hipError_t launch_batch_scan_hits(const BatchEntry* entries, const uint32_t* tile_entry, const uint32_t* entry_req,
                                   BatchHitsWords* words, Hit* hits, Partial* partials, uint32_t tiles,
                                   hipStream_t s);
@@ -1253,10 +1255,12 @@ int first_batch_fast_init_locked(DevCtx* c) {
 // *toff: bytes of the d_ftab / h_ftab buffer in use by the passes in flight.  The fast launches
 // count in the fast class of the profile as batch_run_pass_ex counts them, each piece with its
 // planned nonces, skipped chunks included (mh_search_first's rule for its first_scan launches).
+// stop (mh_search_first_batch_stop): the fast launches are batch_stop<J, MODE>'s, over the same tables
+// in the same order; nothing else of the pass differs.
 int first_batch_run_pass_ex(DevCtx* c, const mh::BatchRequest* reqs, const mh_first_request* src,
                             const std::vector<mh::BatchPiece>& pieces, const mh::BatchTables& t,
-                            const mh::BatchFastTables& f, uint32_t slot_cap, bool rank_major, BatchPending* pend,
-                            size_t* toff, mh_first_result* out) {
+                            const mh::BatchFastTables& f, uint32_t slot_cap, bool rank_major, bool stop,
+                            BatchPending* pend, size_t* toff, mh_first_result* out) {
     mh::FirstBatchFastTables x;
     mh::build_first_batch_tables_ex(t, f, rank_major, &x);
     if (!mh::first_batch_tables_ex_ok(t, f, x, slot_cap)) return fail(MH_EINTERNAL, "internal: bad first-hit batch tables");
@@ -1336,9 +1340,9 @@ int first_batch_run_pass_ex(DevCtx* c, const mh::BatchRequest* reqs, const mh_fi
             tm->var = var_index(l.J, l.mode, (int)f.items[l.item0].args.L);
             MH_HIP(hipEventRecord(tm->start, c->stream));
         }
-        MH_HIP(mh::launch_batch_first(c->dev, l.J, l.mode, (const mh::BatchFirstItem*)(d + o_item),
-                                      (const uint32_t*)(d + o_chunk) + l.chunk0,
-                                      (const uint32_t*)(d + o_corder) + l.chunk0, c->d_partials, l.chunks, c->stream));
+        MH_HIP((stop ? mh::launch_batch_stop : mh::launch_batch_first)(
+            c->dev, l.J, l.mode, (const mh::BatchFirstItem*)(d + o_item), (const uint32_t*)(d + o_chunk) + l.chunk0,
+            (const uint32_t*)(d + o_corder) + l.chunk0, c->d_partials, l.chunks, c->stream));
         if (tm) {
             MH_HIP(hipEventRecord(tm->stop, c->stream));
             c->cnt[0] += 1;
@@ -1365,10 +1369,11 @@ int first_batch_run_pass_ex(DevCtx* c, const mh::BatchRequest* reqs, const mh_fi
     return MH_OK;
 }
 
-// The fused passes of mh_search_first_batch_ex(MH_BATCH_FUSE_FAST), under the device's lock.
+// The fused passes of mh_search_first_batch_ex(MH_BATCH_FUSE_FAST), under the device's lock (stop: of
+// mh_search_first_batch_stop, first_batch_run_pass_ex).
 int first_batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const mh_first_request* src,
                              const std::vector<mh::BatchPiece>& pieces, const std::vector<mh::FastArgs>& args, int passes,
-                             uint32_t slot_cap, mh_first_result* out) {
+                             uint32_t slot_cap, bool stop, mh_first_result* out) {
     DevCtx* c;
     int rc = get_ctx(dev, &c);
     if (rc) return rc;
@@ -1390,7 +1395,7 @@ int first_batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const mh_fir
             rc = first_batch_run_pass(c, reqs, src, t, slot_cap, rank_major, &pend, out);
         } else {
             rc = first_batch_fast_init_locked(c);
-            if (!rc) rc = first_batch_run_pass_ex(c, reqs, src, pieces, t, f, slot_cap, rank_major, &pend, &toff_fast, out);
+            if (!rc) rc = first_batch_run_pass_ex(c, reqs, src, pieces, t, f, slot_cap, rank_major, stop, &pend, &toff_fast, out);
         }
     }
     if (!rc) rc = first_batch_drain(c, reqs, src, &pend, out);
@@ -2033,17 +2038,20 @@ int mh_search_first_batch(int dev, const mh_first_request* reqs, size_t n, mh_fi
     return MH_OK;
 }
 
-int mh_search_first_batch_ex(int dev, const mh_first_request* reqs, size_t n, uint32_t flags, mh_first_result* out) {
-    g_err.clear();
-    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
-    if (!(flags & MH_BATCH_FUSE_FAST)) return mh_search_first_batch(dev, reqs, n, out);
+// mh_search_first_batch_ex(MH_BATCH_FUSE_FAST) and, with stop, mh_search_first_batch_stop (`name`: the
+// caller's, for messages): the same plan, passes and order; stop selects batch_stop<J, MODE> for the
+// fast launches and mh_search_first_ex(MH_FIRST_STOP_RUNNING)'s path for the fallbacks.
+static int first_batch_fused_impl(int dev, const mh_first_request* reqs, size_t n, bool stop, const char* name,
+                           mh_first_result* out) {
     if (n == 0) return MH_OK;
     if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
 #ifdef MH_DEV_HOOKS
     // as mh_search_first_batch: the first-hit kernels have no variants of these hooks
     for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
         if (const char* e = getenv(hook))
-            if (*e) return fail(MH_EINVAL, std::string("mh_search_first_batch_ex does not support ") + hook);
+            if (*e) return fail(MH_EINVAL, std::string(name) + " does not support " + hook);
+#else
+    (void)name;
 #endif
     std::vector<int> status;
     std::vector<mh::BatchRequest> valid;
@@ -2060,18 +2068,31 @@ int mh_search_first_batch_ex(int dev, const mh_first_request* reqs, size_t n, ui
     for (const mh::BatchPiece& p : pieces)
         if (p.kind != 1) passes = std::max(passes, p.pass + 1);
     if (passes) {
-        const int rc = first_batch_run_fused_ex(dev, valid.data(), reqs, pieces, args, passes, slot_cap, out);
+        const int rc = first_batch_run_fused_ex(dev, valid.data(), reqs, pieces, args, passes, slot_cap, stop, out);
         if (rc) return rc;
     }
     for (const mh::BatchPiece& p : pieces) {  // the fallbacks, after the fused passes
         if (p.kind != 1) continue;
         const mh::BatchRequest& r = valid[p.idx];
         mh_first f;
-        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target, 0u, &f);
+        const int rc = search_first_impl(dev, r.pre, r.lower, r.upper, reqs[r.id].target,
+                                         stop ? (uint32_t)MH_FIRST_STOP_RUNNING : 0u, &f);
         if (rc) return rc;
         put_first_result(&out[r.id], f.hash, f.nonce, f.scanned, reqs[r.id].target);
     }
     return MH_OK;
+}
+
+int mh_search_first_batch_ex(int dev, const mh_first_request* reqs, size_t n, uint32_t flags, mh_first_result* out) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (!(flags & MH_BATCH_FUSE_FAST)) return mh_search_first_batch(dev, reqs, n, out);
+    return first_batch_fused_impl(dev, reqs, n, false, "mh_search_first_batch_ex", out);
+}
+
+int mh_search_first_batch_stop(int dev, const mh_first_request* reqs, size_t n, mh_first_result* out) {
+    g_err.clear();
+    return first_batch_fused_impl(dev, reqs, n, true, "mh_search_first_batch_stop", out);
 }
 
 int64_t mh_first_batch_order(const mh_request* reqs, size_t n, int32_t pass, uint32_t* out, int64_t cap) {

@@ -50,6 +50,10 @@
 //                         the first-hit chunk body, chunks dispatched in the host's order and skipped
 //                         above their request's hit; a fifth embedded code object, loaded by the first
 //                         mh_search_first_batch_ex that fuses one.
+//   batch_stop<J, MODE>   (fast_search.hip, -DMH_BATCH -DMH_FIRST -DMH_STOP) batch_first whose waves publish
+//                         a hit when found and leave a running chunk that lies wholly above their
+//                         request's published hit; an eighth embedded code object, loaded by the first
+//                         mh_search_first_batch_stop.
 //   batch_scan_first_slots  batch_scan_first writing partials[slot0 + tile - tile0], as
 //                         batch_scan_slots relates to batch_scan.
 //   merge_segments_first_ex  merge_segments_first with the message state per request, not per tile:
@@ -92,6 +96,8 @@ extern "C" const unsigned char mh_batch_co_begin[];
 extern "C" const unsigned char mh_batch_first_co_begin[];
 // the same source built with -DMH_FIRST -DMH_STOP: stop_scan<J, MODE>, the fast kernels of mh_search_first_ex(MH_FIRST_STOP_RUNNING)
 extern "C" const unsigned char mh_first_stop_co_begin[];
+// the same source built with -DMH_BATCH -DMH_FIRST -DMH_STOP: batch_stop<J, MODE>, the fused fast pieces of mh_search_first_batch_stop
+extern "C" const unsigned char mh_batch_first_stop_co_begin[];
 // the same source built with -DMH_BATCH -DMH_HITS: batch_hits<J, MODE>, the fused fast pieces of mh_search_hits_batch_ex
 extern "C" const unsigned char mh_batch_hits_co_begin[];
 
@@ -787,8 +793,10 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // marker is mh_fast_batch_hits_items at sizeof(BatchHitsItem)
 // or kFastFirstStop, stop_scan<J, MODE> of the seventh (":first_stop"; no hook replaces it): first_scan's
 // parameters and marker
+// or kFastBatchStop, batch_stop<J, MODE> of the eighth (":batch_first_stop"; no hook replaces it):
+// batch_first's parameters, its marker mh_fast_batch_stop_items at sizeof(BatchFirstItem)
 enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4, kFastBatchHits = 5,
-                   kFastFirstStop = 6 };
+                   kFastFirstStop = 6, kFastBatchStop = 7 };
 #ifdef MH_DEV_HOOKS
 std::string batch_module_path() {
     const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
@@ -801,13 +809,14 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                          FastVariant variant = kFastProduct) {
     const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
     const bool bfirst = variant == kFastBatchFirst, bhits = variant == kFastBatchHits, fstop = variant == kFastFirstStop;
+    const bool bstop = variant == kFastBatchStop;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
     const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : batch ? batch_module_path()
-                             : bfirst ? ":batch_first" : bhits ? ":batch_hits" : (co && *co) ? co : "";
+                             : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : (co && *co) ? co : "";
 #else
     const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : batch ? batch_module_path()
-                             : bfirst ? ":batch_first" : bhits ? ":batch_hits" : "";
+                             : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
@@ -818,6 +827,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                              : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
                              : path == ":batch" ? hipModuleLoadData(&m, mh_batch_co_begin)
                              : bfirst       ? hipModuleLoadData(&m, mh_batch_first_co_begin)
+                             : bstop        ? hipModuleLoadData(&m, mh_batch_first_stop_co_begin)
                              : bhits        ? hipModuleLoadData(&m, mh_batch_hits_co_begin)
                              : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
                                             : hipModuleLoad(&m, path.c_str());
@@ -832,6 +842,8 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         const bool marked = batch ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_items") == hipSuccess &&
                                         gsz == sizeof(BatchFastItem)
                             : bfirst ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_first_items") == hipSuccess &&
+                                        gsz == sizeof(BatchFirstItem)
+                            : bstop ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_stop_items") == hipSuccess &&
                                         gsz == sizeof(BatchFirstItem)
                             : bhits ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_hits_items") == hipSuccess &&
                                         gsz == sizeof(BatchHitsItem)
@@ -857,6 +869,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         char name[96];
         snprintf(name, sizeof name,
                  bfirst ? "_ZN2mh11batch_firstILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
+                 : bstop ? "_ZN2mh10batch_stopILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
                  : bhits ? "_ZN2mh10batch_hitsILi%dELi%dEEEvPKNS_13BatchHitsItemEPKjPNS_7PartialE"
                  : first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : fstop ? "_ZN2mh9stop_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
@@ -1104,6 +1117,21 @@ hipError_t launch_batch_first(int dev, int J, int mode, const BatchFirstItem* it
     hipFunction_t fn;
     bool marked = false;
     const hipError_t e = fast_function(dev, J, mode, &fn, &marked, kFastBatchFirst);
+    if (e != hipSuccess) return e;
+    if (!marked) return hipErrorInvalidImage;
+    void* params[] = {&items, &chunk_item, &order, &partials};
+    return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+
+// launch_batch_first with batch_stop<J, mode> of the stopping first-hit batch code object (loaded on
+// dev, the current device, by the first call) in batch_first's place: the same tables, order and grid
+// (mh_search_first_batch_stop).  A code object without its marker at sizeof(BatchFirstItem) is refused.
+hipError_t launch_batch_stop(int dev, int J, int mode, const BatchFirstItem* items, const uint32_t* chunk_item,
+                             const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s) {
+    if (!fast_variant_exists(J, mode) || chunks == 0 || chunks > kMaxBlocksPerLaunch) return hipErrorInvalidValue;
+    hipFunction_t fn;
+    bool marked = false;
+    const hipError_t e = fast_function(dev, J, mode, &fn, &marked, kFastBatchStop);
     if (e != hipSuccess) return e;
     if (!marked) return hipErrorInvalidImage;
     void* params[] = {&items, &chunk_item, &order, &partials};

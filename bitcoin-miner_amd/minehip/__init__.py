@@ -195,15 +195,19 @@ def batch_plan_ex(requests, fuse_fast=True, cap=1 << 16, flags=None):
     return [{f: getattr(buf[i], f) for f, _ in mh_batch_piece._fields_} for i in range(k)]
 
 
-def search_first_batch(requests, dev=0, errors="raise", fuse_fast=False):
+def search_first_batch(requests, dev=0, errors="raise", fuse_fast=False, stop_running=False):
     """[(found, hash, nonce, scanned), ...] of many (msg, lower, upper, target) requests: found,
     hash and nonce exactly what search_first() gives for each, with the small ones fused into one
     GPU pass (mh_search_first_batch).  fuse_fast=True also fuses the fast pieces of the larger
     requests, up to MH_BATCH_FAST_MAX_NONCES nonces each (mh_search_first_batch_ex with
-    MH_BATCH_FUSE_FAST).  Per-request failures as search_batch: raised with the
+    MH_BATCH_FUSE_FAST).  stop_running=True (with fuse_fast=True: its plan is the fused one) gives
+    the same answers from kernels that also leave a running chunk once it lies wholly above a hit
+    of its request (mh_search_first_batch_stop).  Per-request failures as search_batch: raised with the
     request's index, or with errors="return" left in place in the list."""
     if errors not in ("raise", "return"):
         raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
+    if stop_running and not fuse_fast:
+        raise ValueError("stop_running=True requires fuse_fast=True: its plan is the fused one")
     requests = list(requests)
     keep = []
     arr = (mh_first_request * max(1, len(requests)))()
@@ -219,7 +223,9 @@ def search_first_batch(requests, dev=0, errors="raise", fuse_fast=False):
         keep.append(m)
         arr[i].msg, arr[i].len, arr[i].lower, arr[i].upper, arr[i].target = m, len(m), lower, upper, target
     out = (mh_first_result * max(1, len(requests)))()
-    if fuse_fast:
+    if stop_running:
+        _check(lib.mh_search_first_batch_stop(dev, arr, len(requests), out))
+    elif fuse_fast:
         _check(lib.mh_search_first_batch_ex(dev, arr, len(requests), MH_BATCH_FUSE_FAST, out))
     else:
         _check(lib.mh_search_first_batch(dev, arr, len(requests), out))

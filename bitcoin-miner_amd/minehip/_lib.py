@@ -42,7 +42,7 @@ EXPORTS = (
     "mh_search_first", "mh_search_first_batch", "mh_first_batch_order", "mh_search_hits",
     "mh_search_hits_batch", "mh_hits_batch_regions", "mh_search_batch_ex", "mh_batch_plan_ex",
     "mh_search_first_batch_ex", "mh_first_batch_order_ex", "mh_search_hits_batch_ex", "mh_hits_batch_regions_ex",
-    "mh_miner_handle_batch_ex", "mh_search_first_ex",
+    "mh_miner_handle_batch_ex", "mh_search_first_ex", "mh_search_first_batch_stop",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -211,6 +211,8 @@ def _load():
                                        ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64]
     L.mh_search_first_batch_ex.argtypes = [ctypes.c_int, ctypes.POINTER(mh_first_request), sz, ctypes.c_uint32,
                                            ctypes.POINTER(mh_first_result)]
+    L.mh_search_first_batch_stop.argtypes = [ctypes.c_int, ctypes.POINTER(mh_first_request), sz,
+                                             ctypes.POINTER(mh_first_result)]
     L.mh_first_batch_order_ex.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.c_uint32, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64]
     L.mh_search_hits_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hit), sz,

@@ -68,6 +68,15 @@ def batch_first_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def batch_first_stop_code_object():
+    """The embedded code object of the stopping first-hit batch kernels (mh_search_first_batch_stop):
+    batch_stop<J, MODE>, fast_search.hip built with -DMH_BATCH -DMH_FIRST -DMH_STOP
+    (mh_batch_first_stop_co_begin .. mh_batch_first_stop_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_first_stop_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_first_stop_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def batch_hits_code_object():
     """The embedded code object of the hits batch kernels (mh_search_hits_batch_ex):
     batch_hits<J, MODE>, fast_search.hip built with -DMH_BATCH -DMH_HITS
@@ -203,6 +212,12 @@ def batch_first_kernel_resources(co=None):
     """The same of the embedded batch_first<J, MODE> kernels (or of those of code object `co`)."""
     return fast_kernel_resources(batch_first_code_object() if co is None else co,
                                  r"_ZN2mh11batch_firstILi(\d+)ELi(\d+)E")
+
+
+def batch_first_stop_kernel_resources(co=None):
+    """The same of the embedded batch_stop<J, MODE> kernels (or of those of code object `co`)."""
+    return fast_kernel_resources(batch_first_stop_code_object() if co is None else co,
+                                 r"_ZN2mh10batch_stopILi(\d+)ELi(\d+)E")
 
 
 def batch_hits_kernel_resources(co=None):

@@ -186,7 +186,8 @@ int mh_search_first(int dev, const uint8_t *msg, size_t len, uint64_t lower, uin
  * nonces of the range actually hashed, counted on the device by the waves themselves:
  * upper - lower + 1 when nothing qualifies, else within [nonce - lower + 1, upper - lower + 1].
  * Errors and conventions are mh_search_first's.  Opt-in: DESIGN.md section 3 has what the poll
- * costs a search without an early hit.  The batched forms do not take the flag.
+ * costs a search without an early hit.  The batched forms do not take the flag (the stopping
+ * batch is a call of its own, mh_search_first_batch_stop below).
  * Additive in ABI 5 (no existing struct or function changes). */
 #define MH_FIRST_STOP_RUNNING 1u
 int mh_search_first_ex(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
@@ -249,6 +250,29 @@ int mh_search_first_batch(int dev, const mh_first_request *reqs, size_t n, mh_fi
  * otherwise.  Errors and per-request statuses are mh_search_first_batch's.  Additive in ABI 5. */
 int mh_search_first_batch_ex(int dev, const mh_first_request *reqs, size_t n, uint32_t flags,
                              mh_first_result *out);
+
+/* mh_search_first_batch_ex(MH_BATCH_FUSE_FAST) whose running chunks stop, as
+ * mh_search_first_ex(MH_FIRST_STOP_RUNNING)'s do.  An entry point of its own and not a flag: the
+ * flag bits of mh_search_first_batch_ex other than MH_BATCH_FUSE_FAST stay MH_EINVAL.  The plan is
+ * mh_batch_plan_ex(MH_BATCH_FUSE_FAST)'s and the dispatch order
+ * mh_first_batch_order_ex(MH_BATCH_FUSE_FAST)'s (MINEHIP_FIRST_BATCH_ORDER included); the generic
+ * tiles, the merge, the one copy each way per pass and the one host synchronise per call are
+ * mh_search_first_batch_ex's.  The fast pieces of one layout of a pass run as one launch of
+ * batch_stop<J, MODE> (a code object of its own, loaded by the first call that asks for it):
+ * batch_first's tables, order and skip of an unbegun chunk, around stop_scan's chunk body -- a wave
+ * lowers its request's word when it finds a hit, and once per group of ten nonces, outside the
+ * per-nonce loop, polls that word and leaves its chunk when every nonce of the chunk lies above
+ * it.  The word is the request's own, the one its generic tiles lower too, so a hit of any piece
+ * or tile of a request stops that request's running chunks and no other's.  Nothing waits on the
+ * word.  A fallback request runs through the mh_search_first_ex(MH_FIRST_STOP_RUNNING) path after
+ * the fused passes.
+ * Per request, found, hash and nonce are bit for bit mh_search_first's, whatever the batch holds,
+ * the passes, the order or the timing (DESIGN.md section 3 has the argument); scanned is counted
+ * by the waves themselves: upper - lower + 1 when nothing qualifies, else within
+ * [nonce - lower + 1, upper - lower + 1].  Errors, per-request statuses, n == 0 and NULL arrays are
+ * mh_search_first_batch_ex's.  Opt-in: DESIGN.md section 3 has what was measured, the poll's cost
+ * for a batch without a hit included.  Additive in ABI 5 (no existing struct or function changes). */
+int mh_search_first_batch_stop(int dev, const mh_first_request *reqs, size_t n, mh_first_result *out);
 
 /* ---- every hit: all nonces of a range whose hash meets a target ---------- */
 

@@ -25,6 +25,19 @@ What the numbers are read for (DESIGN.md §3 "Batched first-hit search with fuse
   order        c against d with hits, in time and in scanned share
 
     python tools/first_batch_fast_latency.py [--rounds 15] [--out profiles/first_batch_fast_latency.json]
+
+--stop measures mh_search_first_batch_stop instead (DESIGN.md §3 "Batched first-hit search whose running
+chunks stop"): the same sizes and targets, two variants in alternating rounds of one process,
+
+  c  minehip.search_first_batch(reqs, fuse_fast=True): the yardstick, the code objects every earlier
+     commit ships
+  s  the same call with stop_running=True: batch_stop<J, MODE> for the fast launches
+
+with medians, interquartile ranges, kernel time and the `scanned` share of both.  At target 0
+nothing can be skipped, so s against c there is what the poll costs: `poll_rule` says per size
+whether s is slower than c by more than c's own interquartile range.
+
+    python tools/first_batch_fast_latency.py --stop [--rounds 15] [--out profiles/first_batch_stop_latency.json]
 """
 import argparse
 import json
@@ -122,15 +135,73 @@ def run_case(k, nonces, target, rounds):
     return res
 
 
+def run_stop_case(k, nonces, target, rounds):
+    """--stop: search_first_batch(fuse_fast=True) against the same call with stop_running=True."""
+    ranges = [("cmu440-%02d" % i, 0, nonces - 1) for i in range(k)]
+    reqs = [r + (target,) for r in ranges]
+    variants = {"c": lambda: minehip.search_first_batch(reqs, fuse_fast=True),
+                "s": lambda: minehip.search_first_batch(reqs, fuse_fast=True, stop_running=True)}
+    got = {}
+    for _ in range(3):  # warm both paths
+        for name, fn in variants.items():
+            got[name] = fn()
+    assert [g[:3] for g in got["c"]] == [g[:3] for g in got["s"]], "the variants differ"
+    t = {name: [] for name in variants}
+    scanned = {name: [] for name in variants}
+    names, rng = list(variants), random.Random(440)
+    for _ in range(rounds):  # both once per round, in a shuffled order
+        rng.shuffle(names)
+        for name in names:
+            dt, r = timed(variants[name])
+            t[name].append(dt)
+            scanned[name].append(sum(g[3] for g in r))
+    res = {"requests": k, "nonces_each": nonces, "target": target, "rounds": rounds,
+           "found": sum(g[0] for g in got["c"]), "plan": plan_summary(ranges)}
+    if res["found"]:  # the nonces a sequential scan would need: up to each request's first hit
+        res["needed_share"] = round(sum(g[2] + 1 if g[0] else nonces for g in got["c"]) / (k * nonces), 6)
+    for name, ts in t.items():
+        res[name] = quartiles(ts)
+        res[name]["kernel_ms"] = kernel_ms(variants[name])
+        ss = sorted(scanned[name])
+        res[name]["scanned_median"] = ss[len(ss) // 2]
+        res[name]["scanned_share"] = round(ss[len(ss) // 2] / (k * nonces), 6)
+    res["s"]["speedup_vs_c"] = round(res["c"]["median_ms"] / res["s"]["median_ms"], 3)
+    res["s"]["not_slower_than_c"] = res["s"]["median_ms"] <= res["c"]["median_ms"] + res["c"]["iqr_ms"]
+    return res
+
+
+def main_stop(a):
+    out = {"cases": {}}
+    for size, k, nonces in SIZES:
+        if size not in a.cases.split(","):
+            continue
+        for tname, target in TARGETS:
+            name = f"{size}_{tname}"
+            out["cases"][name] = run_stop_case(k, nonces, target, a.rounds)
+            print(name, json.dumps(out["cases"][name]), flush=True)
+    zero = {n: r for n, r in out["cases"].items() if n.endswith("_zero")}
+    out["poll_rule"] = {"s_not_slower_than_c_at_zero": {n: r["s"]["not_slower_than_c"] for n, r in zero.items()},
+                        "s_over_c_at_zero": {n: round(r["s"]["median_ms"] / r["c"]["median_ms"], 4) for n, r in zero.items()}}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "first_batch_fast_latency.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--cases", default=",".join(s[0] for s in SIZES))
+    ap.add_argument("--stop", action="store_true", help="measure search_first_batch(stop_running=True) against fuse_fast=True")
     a = ap.parse_args()
     if a.rounds < 11:
         ap.error("--rounds: at least 11")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "first_batch_stop_latency.json" if a.stop else "first_batch_fast_latency.json")
     os.environ["MINEHIP_BATCH_FAST_MAX"] = str((1 << 64) - 1)
+    if a.stop:
+        return main_stop(a)
     out = {"cases": {}}
     for size, k, nonces in SIZES:
         if size not in a.cases.split(","):
