@@ -52,8 +52,8 @@ def split_line(m):
 # or hits_scan<J, MODE> of the -DMH_HITS build or batch_fast<J, MODE> of the -DMH_BATCH builds or
 # batch_first<J, MODE> of the -DMH_BATCH -DMH_FIRST build or batch_hits<J, MODE> of the -DMH_BATCH
 # -DMH_HITS build or stop_scan<J, MODE> of the -DMH_FIRST -DMH_STOP build or batch_stop<J, MODE> of
-# the -DMH_BATCH -DMH_FIRST -DMH_STOP build
-KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits|9stop_scan|10batch_stop)\S*:")
+# the -DMH_BATCH -DMH_FIRST -DMH_STOP build or hits_stop<J, MODE> of the -DMH_HITS -DMH_STOP build
+KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits|9stop_scan|10batch_stop|9hits_stop)\S*:")
 
 
 def split(text, k, pattern=None, phase=None):

@@ -17,7 +17,9 @@
    that asks for MH_FIRST_STOP_RUNNING, and the stopping first-hit batch
    kernels of mh_search_first_batch_stop (-DMH_BATCH -DMH_FIRST -DMH_STOP,
    build/fast_batch_first_stop.hsaco), loaded per device by the first such
-   call that fuses a fast piece. */
+   call that fuses a fast piece, and the stopping hits kernels of
+   mh_search_first_hits (-DMH_HITS -DMH_STOP, build/fast_hits_stop.hsaco),
+   loaded per device by the first such call. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -83,4 +85,12 @@ mh_batch_first_stop_co_begin:
     .globl mh_batch_first_stop_co_end
 mh_batch_first_stop_co_end:
     .size mh_batch_first_stop_co_begin, mh_batch_first_stop_co_end - mh_batch_first_stop_co_begin
+    .p2align 12
+    .globl mh_hits_stop_co_begin
+    .type mh_hits_stop_co_begin, @object
+mh_hits_stop_co_begin:
+    .incbin "fast_hits_stop.hsaco"
+    .globl mh_hits_stop_co_end
+mh_hits_stop_co_end:
+    .size mh_hits_stop_co_begin, mh_hits_stop_co_end - mh_hits_stop_co_begin
     .section .note.GNU-stack,"",@progbits

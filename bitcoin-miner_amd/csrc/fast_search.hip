@@ -39,6 +39,10 @@
 // the same passes): batch_first's table, order and grid around stop_scan's chunk body,
 // which polls its request's word through the item, an eighth embedded code object that
 // mh_search_first_batch_stop loads; likewise (everything of it sits under MH_STOP).
+// -DMH_HITS -DMH_STOP builds hits_stop<J, MODE> (build/fast_hits_stop.hsaco, through the same passes;
+// DESIGN.md §3): hits_scan whose hits also count in slices of the range, whose waves publish a bound
+// once the slices hold k hits and leave a running chunk that lies wholly above it, a ninth embedded
+// code object that mh_search_first_hits loads; likewise (everything of it sits under MH_HITS and MH_STOP).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -216,6 +220,30 @@ struct HitsKernArgs {
 __device__ __forceinline__ const HitsArgs& hits_args(const FastArgs& a) {
     return ((const HitsKernArgs*)&a)->h;
 }
+#ifdef MH_STOP
+// The parameters of hits_stop<J, MODE> (below) as the kernarg segment holds them: HitsStopArgs
+// begins with a HitsArgs, so hits_args serves this build unchanged.
+struct HitsStopKernArgs {
+    FastArgs a;
+    Partial* partials;
+    HitsStopArgs h;
+};
+static_assert(__builtin_offsetof(HitsStopKernArgs, h.h) == __builtin_offsetof(HitsKernArgs, h),
+              "hits_args finds the HitsArgs that HitsStopArgs begins with");
+__device__ __forceinline__ const HitsStopArgs& hits_stop_args(const FastArgs& a) {
+    return ((const HitsStopKernArgs*)&a)->h;
+}
+// No nonce of chunk blk is smaller: lane 0's first, attained, so exact (the first-hit builds'
+// floor: last-digit layouts U * 10^L, Early layouts spread(U) * u_mul, spread strictly increasing).
+template <int MODE>
+__device__ __forceinline__ uint64_t hits_floor(const FastArgs& a, uint32_t blk) {
+    const uint64_t u0 = a.u_start + (uint64_t)blk * kBlockThreads;
+    if constexpr (MODE < (int)kModeOneEarly)
+        return u0 * a.pow10L;
+    else
+        return spread(u0, a.hole, a.hole_w) * a.u_mul;
+}
+#endif
 #endif
 template <int J, int MODE>
 __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restrict__ partials, const uint32_t blk) {
@@ -374,6 +402,28 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
         }
 #endif
 #endif
+#ifdef MH_HITS
+#ifdef MH_STOP
+        // hits_stop: the same poll, of the search's bound word (layout.hpp HitsStopArgs): at least k
+        // hits of the range are <= its value, so once every nonce of this chunk lies above it
+        // (hits_floor, attained, so exact) none of them is among the k smallest hits, and the wave
+        // leaves the loop for the chunk's end -- block_min, its barriers and the chunk's Partial,
+        // which the host then does not use.  Read as stop_scan reads its word: a
+        // relaxed agent-scope load (a vector load past this CU's L1, never the scalar cache), made
+        // wave-uniform, through a kernarg pointer laundered here so that neither the word's address
+        // nor the floor is held across the per-nonce loop.  A poll, never a wait.
+        {
+            using KHStop = __attribute__((address_space(4))) const HitsStopKernArgs;
+            KHStop* kb = (KHStop*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kb));
+            const HitsStopKernArgs& bk = *(const HitsStopKernArgs*)kb;
+            const uint64_t seen = __hip_atomic_load(bk.h.bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t word = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(seen >> 32)) << 32) |
+                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)seen);
+            if (hits_floor<MODE>(bk.a, blk) > word) break;
+        }
+#endif
+#endif
         // the L-1 digits of g: wave-uniform, so this is SALU work.  Into word J (cj) or word
         // J - 1 (cjm; the Early layouts put every group digit in word J)
         uint32_t cj = 0u, cjm = 0u, gq = g;
@@ -430,6 +480,17 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 asm volatile("" : "+v"(kwg[t]));
             }
 #endif
+#ifdef MH_HITS
+        // hits_stop: likewise (its group loop holds the poll's break; left to the compiler, ten
+        // One and Pre layouts redo one to four of these adds on every nonce)
+        uint32_t kwg[64];
+#pragma unroll
+        for (int t = 16; t < (BM == kModeTwo ? 64 : 63); ++t)
+            if (MH_G(t) && t > J) {
+                kwg[t] = K[t] + wg[t];
+                asm volatile("" : "+v"(kwg[t]));
+            }
+#endif
 #endif
         // round J-1 reads the group-level word J-1 (Early: it is run-level, done above)
         uint32_t ga = ra, gb = rb, gc = rc, gd = rd, ge = re, gf = rf, gG = rg, gh = rh;
@@ -443,6 +504,9 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
         // E = (gd + t1J) + inc are two adds per nonce where t1 = t1J + inc, A = t1 + t2J, E = gd + t1
         // are three, from two group-level registers instead of three
         const uint32_t aJ = t1J + t2J, eJ = gd + t1J;
+#endif
+#ifdef MH_HITS
+        const uint32_t aJ = t1J + t2J, eJ = gd + t1J;  // hits_stop: likewise
 #endif
 #endif
 
@@ -469,8 +533,12 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
 #ifdef MH_BATCH
             uint32_t A = aJ + inc, B = ga, C = gb, D = gc, E = eJ + inc, F = ge, G = gf, H = gG;
 #else
+#ifdef MH_HITS
+            uint32_t A = aJ + inc, B = ga, C = gb, D = gc, E = eJ + inc, F = ge, G = gf, H = gG;
+#else
             const uint32_t t1 = t1J + inc;
             uint32_t A = t1 + t2J, B = ga, C = gb, D = gc, E = gd + t1, F = ge, G = gf, H = gG;
+#endif
 #endif
 #else
             const uint32_t t1 = t1J + inc;
@@ -487,8 +555,14 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                              (t >= 16 && MH_R(t)) ? kwr[t] : (t >= 16 && MH_G(t)) ? kwg[t]
                                                   : K[t] + (MH_N(t) ? x[t] : wr[t]));
 #else
+#ifdef MH_HITS
+                    round_kw(A, B, C, D, E, F, G, H,
+                             (t >= 16 && MH_R(t)) ? kwr[t] : (t >= 16 && MH_G(t)) ? kwg[t]
+                                                  : K[t] + (MH_N(t) ? x[t] : wr[t]));
+#else
                     round_kw(A, B, C, D, E, F, G, H,
                              (t >= 16 && MH_R(t)) ? kwr[t] : K[t] + (MH_N(t) ? x[t] : (MH_G(t) ? wg[t] : wr[t])));
+#endif
 #endif
 #else
                     round_kw(A, B, C, D, E, F, G, H,
@@ -510,8 +584,14 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                              (t >= 16 && MH_R(t)) ? kwr[t] : (t >= 16 && MH_G(t)) ? kwg[t]
                                                   : K[t] + (MH_N(t) ? x[t] : wr[t]));
 #else
+#ifdef MH_HITS
+                    round_kw(A, B, C, D, E, F, G, H,
+                             (t >= 16 && MH_R(t)) ? kwr[t] : (t >= 16 && MH_G(t)) ? kwg[t]
+                                                  : K[t] + (MH_N(t) ? x[t] : wr[t]));
+#else
                     round_kw(A, B, C, D, E, F, G, H,
                              (t >= 16 && MH_R(t)) ? kwr[t] : K[t] + (MH_N(t) ? x[t] : (MH_G(t) ? wg[t] : wr[t])));
+#endif
 #endif
 #else
                     round_kw(A, B, C, D, E, F, G, H,
@@ -574,6 +654,34 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                         const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
                         const uint32_t lead = (uint32_t)__builtin_ctzll(hm);
                         unsigned long long taken = 0ull;
+#ifdef MH_STOP
+                        // hits_stop: each hit first counts in its slice (layout.hpp HitsStopArgs), by
+                        // the same scalar walk, and the counts are back before the cursor advances:
+                        // whoever gets a cursor value back finds every hit it stands for in the slices
+                        // (the arguments through a kernarg pointer laundered here, in the rare branch: read
+                        // through `a` they are loaded ahead of the loops and held in SGPRs across the
+                        // per-nonce loop, which costs the Two layouts' loops three to six v_readlane_b32)
+                        using KHits2 = __attribute__((address_space(4))) const HitsStopKernArgs;
+                        KHits2* kq = (KHits2*)__builtin_amdgcn_kernarg_segment_ptr();
+                        asm volatile("" : "+s"(kq));
+                        const HitsStopArgs& hs = ((const HitsStopKernArgs*)kq)->h;
+                        {
+                            uint64_t sm = hm;
+                            uint32_t back = 0u;
+                            do {
+                                const uint32_t l = (uint32_t)__builtin_ctzll(sm);
+                                sm &= sm - 1ull;
+                                uint64_t cn;
+                                if constexpr (!EARLY)
+                                    cn = (wave_u0 + l) * a.pow10L + q;
+                                else
+                                    cn = spread(wave_u0 + l, a.hole, a.hole_w) * a.u_mul + spread(g, a.g_hole, 1u) * a.g_mul +
+                                         i * a.i_mul;
+                                if (lane == lead) back += atomicAdd(first_hits_slice(hs, cn), 1u);
+                            } while (sm);
+                            asm volatile("" ::"v"(back) : "memory");
+                        }
+#endif
                         if (lane == lead) taken = atomicAdd(ha.cursor, (unsigned long long)__builtin_popcountll(hm));
                         uint64_t slot =
                             ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(taken >> 32), (int)lead) << 32) |
@@ -592,6 +700,10 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                             if (slot < ha.cap && lane == lead) ha.hits[slot] = Hit{((uint64_t)c0 << 32) | c1, cn};
                             ++slot;
                         } while (hm);
+#ifdef MH_STOP
+                        // the cursor value this wave got back plus its own hits reaches k: publish
+                        if (slot >= hs.k) publish_first_hits_bound(hs, lane);
+#endif
                     }
                 }
 #endif
@@ -681,6 +793,13 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
         atomicAdd(first_args(a).scanned, (unsigned long long)__builtin_popcountll(valid_mask) * g * 10ull);
 #endif
     if (wbh0 == (uint32_t)(first_args(a).target >> 32) && wbh1 == 0u) wbh0 = 0u;  // lim -> k0
+#endif
+#ifdef MH_HITS
+#ifdef MH_STOP
+    // scanned: what this wave hashed -- its valid lanes x the groups it ran x 10 -- one atomic per wave
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+        atomicAdd(hits_stop_args(a).scanned, (unsigned long long)__builtin_popcountll(valid_mask) * g * 10ull);
+#endif
 #endif
     uint64_t hash = ((uint64_t)wbh0 << 32) | wbh1;  // wave-uniform: the wave step of block_min
     uint64_t nonce = wbn;                            // is a no-op, the LDS step joins the waves
@@ -851,6 +970,69 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_fast(
 #endif
 #else
 #ifndef MH_FIRST
+#ifdef MH_HITS
+#ifdef MH_STOP
+// ---------------------------------------------------------------------------
+// hits_stop<J, MODE>: the same chunks with the hits append, for mh_search_first_hits
+// ---------------------------------------------------------------------------
+// claim_chunk with one more word per claim: thread 0 reads the search's bound word beside the
+// claim (all ones: fewer than k hits counted so far); a chunk all of whose nonces are larger is
+// skipped -- thread 0 writes the sentinel its slot's merge expects and claims again -- so the
+// workgroup only ever sees a chunk to run, or the end.  The word only ever decreases, and whenever
+// it holds B at least k hits of the range are <= B (layout.hpp HitsStopArgs), so no chunk that
+// holds one of the k smallest hits is ever skipped, whatever value a claim happens to see: a stale
+// read only skips less.  Static launches (no counter): the workgroup's one chunk is blockIdx.x, and
+// skipping it ends the workgroup.  A chunk that is run counts what its waves hash (fast_chunk).
+template <int MODE>
+__device__ __forceinline__ uint32_t claim_below_bound(Partial* __restrict__ partials) {
+    __shared__ uint32_t s_next;
+    if (threadIdx.x == 0) {
+        uint32_t b;
+        for (;;) {
+            // the arguments through a pointer laundered per claim, as the chunk body's
+            using KArgs = __attribute__((address_space(4))) const HitsStopKernArgs;
+            KArgs* k = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(k));
+            const FastArgs& a = ((const HitsStopKernArgs*)k)->a;
+            const HitsStopArgs& h = ((const HitsStopKernArgs*)k)->h;
+            b = a.counter ? atomicAdd(a.counter, 1u) : blockIdx.x;
+            if (b >= a.n_chunks) break;
+            const uint64_t seen = __hip_atomic_load(h.bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (hits_floor<MODE>(a, b) <= seen) break;  // run it
+            uint64_t ones = ~0ull;
+            asm volatile("" : "+v"(ones));  // made here, not held across the chunk
+            partials[b] = Partial{ones, ones};
+            if (!a.counter) {
+                b = ~0u;  // past every n_chunks
+                break;
+            }
+        }
+        s_next = b;
+    }
+    __syncthreads();
+    const uint32_t blk = __builtin_amdgcn_readfirstlane(s_next);  // one value per workgroup: scalar
+    __syncthreads();  // every wave has read it before thread 0 may overwrite it
+    return blk;
+}
+
+// fast_search's loop over claim_below_bound: every chunk the loop sees is run, and may be left early.
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void hits_stop(const FastArgs a,
+                                                                         Partial* __restrict__ partials,
+                                                                         const HitsStopArgs) {
+    using KArgs = __attribute__((address_space(4))) const HitsStopKernArgs;
+    KArgs* const kp = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t blk = claim_below_bound<MODE>(partials);
+    while (blk < a.n_chunks) {
+        KArgs* k = kp;
+        asm volatile("" : "+s"(k));
+        fast_chunk<J, MODE>(((const HitsStopKernArgs*)k)->a, partials, blk);
+        if (!a.counter) break;
+        blk = claim_below_bound<MODE>(partials);
+    }
+}
+#endif
+#endif
 template <int J, int MODE>
 #ifdef MH_HITS
 // hits_scan<J, MODE>: fast_search with the append of every hit in its chunk body, for
@@ -1031,8 +1213,13 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 #else
 #ifndef MH_FIRST
 #ifdef MH_HITS
+#ifdef MH_STOP
+#define MH_INST(j, m) \
+    template __global__ void hits_stop<j, m>(const FastArgs, Partial* __restrict__, const HitsStopArgs);
+#else
 #define MH_INST(j, m) \
     template __global__ void hits_scan<j, m>(const FastArgs, Partial* __restrict__, const HitsArgs);
+#endif
 #else
 #define MH_INST(j, m) template __global__ void fast_search<j, m>(const FastArgs, Partial* __restrict__);
 #endif

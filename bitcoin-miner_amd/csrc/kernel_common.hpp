@@ -96,5 +96,54 @@ __device__ __forceinline__ void add_word(uint32_t (&w)[NW], uint32_t wi, uint32_
     for (int x = 0; x < NW; ++x) w[x] += (wi == (uint32_t)x) ? v : 0u;
 }
 
+// mh_search_first_hits (layout.hpp HitsStopArgs): lower the search's bound word from the slice
+// counters.  Called by a whole wave (every lane active) that has just appended hits and got back a
+// cursor value which, with its own hits, reaches k -- on the rare hit branch only.  Lane l sums
+// counters 16 l .. 16 l + 15 (relaxed agent-scope vector loads, past this CU's L1: other
+// workgroups' atomics write them), a scalar walk over the lanes' sums finds the lane whose slices
+// take the prefix sum to k, and that lane reads its counters again to find the slice and lowers
+// the word to the slice's last nonce (first_hits_slice_end: no 64-bit overflow).  The counters only
+// grow, and any values no larger than the true counts give a valid bound, so the two readings need
+// not agree.  Every appending wave adds its hits to their slices, and has the counts back, before
+// it advances the cursor, so the counts read here hold at least k hits; were they seen lower all
+// the same, nothing is published: never a wrong bound.  The counters are summed, not kept, and the
+// owner's loop stays rolled: sixteen counters held in VGPRs across the walk cost the kernel around
+// this rare branch registers, and its per-nonce loop two or three VALU instructions.
+__device__ __forceinline__ void publish_first_hits_bound(const HitsStopArgs& hs, uint32_t lane) {
+    constexpr uint32_t PER = kFirstHitsSlices / 64u;
+    const uint32_t k = (uint32_t)hs.k;  // <= MH_HITS_MAX_CAP = 2^20
+    const uint32_t* mine = hs.slices + lane * PER;
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) sum += __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t ls = sum < (uint64_t)k ? (uint32_t)sum : k;  // clamped: the walk's sums stay below 2^21
+    uint32_t acc = 0u, owner = 64u;
+    for (uint32_t l = 0; l < 64u; ++l) {
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)ls, (int)l);
+        if (acc + v >= k) {
+            owner = l;
+            break;
+        }
+        acc += v;
+    }
+    if (lane == owner) {  // owner == 64: the counts seen hold fewer than k hits
+        uint64_t pre = acc;
+        uint32_t s = 0u;
+#pragma nounroll
+        for (; s < PER - 1u; ++s) {  // (the last counter is not read: the prefix reaches k there at the latest)
+            pre += __hip_atomic_load(mine + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (pre >= (uint64_t)k) break;
+        }
+        atomicMin(hs.bound, (unsigned long long)first_hits_slice_end(hs.lower, hs.span, hs.shift, lane * PER + s));
+    }
+}
+
+// The slice counter of nonce n, for the add of an appended hit (n lies in the range; the index is
+// cut to the counters all the same).
+__device__ __forceinline__ uint32_t* first_hits_slice(const HitsStopArgs& hs, uint64_t n) {
+    const uint64_t s = (n - hs.lower) >> hs.shift;
+    return hs.slices + (s < (uint64_t)kFirstHitsSlices ? (uint32_t)s : kFirstHitsSlices - 1u);
+}
+
 }  // namespace dev
 }  // namespace mh

@@ -168,6 +168,53 @@ struct HitsArgs {
     uint64_t cap;
 };
 
+// ---- the first k hits (mh_search_first_hits) ----
+// The range [lower, upper] (span = upper - lower) is cut into at most kFirstHitsSlices slices of
+// 2^shift nonces, shift the smallest value with kFirstHitsSlices << shift >= span + 1; every hit
+// that is appended also counts in its slice, and once the counts hold k hits the end of the first
+// slice whose prefix sum reaches k is a nonce no larger nonce than which can belong to the k
+// smallest hits: the bound the kernels publish (first_hits_bound) and skip or leave chunks by.
+constexpr uint32_t kFirstHitsSlices = 1024;
+constexpr uint32_t first_hits_shift(uint64_t span) {
+    uint32_t shift = 0;
+    while ((span >> shift) >= kFirstHitsSlices) ++shift;  // span >> shift < 1024  <=>  1024 << shift >= span + 1
+    return shift;
+}
+constexpr uint32_t first_hits_slices(uint64_t span, uint32_t shift) { return (uint32_t)(span >> shift) + 1u; }
+// The last nonce of slice s: lower + min(span, ((s + 1) << shift) - 1), without leaving 64 bits
+// (the last slice's end is cut to the range's, and (s + 1) << shift is only formed below it).
+constexpr uint64_t first_hits_slice_end(uint64_t lower, uint64_t span, uint32_t shift, uint32_t s) {
+    return lower + ((uint64_t)s >= (span >> shift) ? span : (((uint64_t)s + 1u) << shift) - 1u);
+}
+// The value published from the slice counts counts[0 .. first_hits_slices): all ones while they
+// sum to fewer than k.
+constexpr uint64_t first_hits_bound(uint64_t lower, uint64_t span, uint32_t shift, uint64_t k, const uint32_t* counts) {
+    uint64_t sum = 0;
+    const uint32_t n = first_hits_slices(span, shift);
+    for (uint32_t s = 0; s < n; ++s) {
+        sum += counts[s];
+        if (sum >= k) return first_hits_slice_end(lower, span, shift, s);
+    }
+    return ~0ull;
+}
+
+// Extra kernel parameters of the stopping hits kernels (hits_stop<J, MODE> of the
+// build/fast_hits_stop.hsaco code object, generic_scan_hits_stop), after the product kernels' own
+// two: a HitsArgs first, so the append reads it as hits_scan does, then the search's k, its bound
+// word (all ones at the start, only ever lowered), the kFirstHitsSlices slice counters, the range
+// the slices cut, and the count of nonces hashed.
+struct HitsStopArgs {
+    HitsArgs h;
+    uint64_t k;
+    unsigned long long* bound;    // whenever it holds B < 2^64-1, at least k hits of the range are <= B
+    uint32_t* slices;             // kFirstHitsSlices counters, zeroed by the host
+    uint64_t lower;
+    uint64_t span;                // upper - lower
+    uint32_t shift;
+    uint32_t pad_;                // 0
+    unsigned long long* scanned;  // nonces hashed
+};
+
 // ---- batched search (batch_scan / merge_segments) ----
 // Many small Requests in one launch.  A lane's unit of work is an aligned decade, the ten nonces
 // 10u .. 10u+9: they share their digit count, so u is formatted once for the ten.  A tile is one

@@ -52,6 +52,10 @@ hipError_t launch_fast_hits(int dev, int J, int mode, const FastArgs& a, Partial
                             hipStream_t s);
 hipError_t launch_generic_scan_hits(const GenArgs& a, Partial* partials, uint32_t blocks, const HitsArgs& h,
                                     hipStream_t s);
+hipError_t launch_fast_hits_stop(int dev, int J, int mode, const FastArgs& a, Partial* partials, const HitsStopArgs& h,
+                                 hipStream_t s);
+hipError_t launch_generic_scan_hits_stop(const GenArgs& a, Partial* partials, uint32_t blocks, const HitsStopArgs& h,
+                                         hipStream_t s);
 hipError_t launch_batch_scan(const BatchEntry* entries, const uint32_t* tile_entry, Partial* partials, uint32_t tiles,
                              hipStream_t s);
 hipError_t launch_merge_segments(const Partial* partials, const uint32_t* seg, Partial* results, uint32_t requests,
@@ -180,6 +184,11 @@ struct DevCtx {
     uint64_t* d_hcursor = nullptr;  // hits of the scan in flight
     uint64_t* h_hcursor = nullptr;  // pinned
     const mh::HitsArgs* hits = nullptr;  // set while an mh_search_hits enqueues its pieces
+    // the first k hits (mh_search_first_hits), allocated by the first such call; the hit buffer and the cursor are mh_search_hits'
+    uint64_t* d_fhits = nullptr;    // [0] the bound word, [1] nonces scanned
+    uint32_t* d_slices = nullptr;   // kFirstHitsSlices slice counters
+    uint64_t* h_fhits = nullptr;    // pinned: the scanned count
+    const mh::HitsStopArgs* hits_stop = nullptr;  // set while an mh_search_first_hits enqueues its pieces
     // batched hits (mh_search_hits_batch), allocated by the first such call; the hit buffer is d_hits
     mh::BatchHitsResult* d_hres = nullptr;  // one result per request of the passes in flight
     mh::BatchHitsResult* h_hres = nullptr;  // pinned
@@ -430,6 +439,11 @@ int enqueue_piece(DevCtx* c, const mh::Piece& p, const mh::PlanOpts& opt, bool s
             MH_HIP(mh::launch_fast_first(c->dev, p.J, p.mode, fa, out, *c->first, c->first_stop, s));
         else
             MH_HIP(mh::launch_generic_scan_first(ga, out, blocks, *c->first, s));
+    } else if (c->hits_stop) {  // mh_search_first_hits: the stopping hits kernels over the same pieces
+        if (p.kind == 0)
+            MH_HIP(mh::launch_fast_hits_stop(c->dev, p.J, p.mode, fa, out, *c->hits_stop, s));
+        else
+            MH_HIP(mh::launch_generic_scan_hits_stop(ga, out, blocks, *c->hits_stop, s));
     } else if (c->hits) {  // mh_search_hits: the hits kernels over the same pieces
         if (p.kind == 0)
             MH_HIP(mh::launch_fast_hits(c->dev, p.J, p.mode, fa, out, *c->hits, s));
@@ -714,6 +728,39 @@ int hits_scan_range(DevCtx* c, const mh::Prefix& pre, uint64_t lower, uint64_t u
     return MH_OK;
 }
 
+bool hit_by_nonce(const mh::Hit& x, const mh::Hit& y) { return x.nonce < y.nonce; }
+
+// The window walk of mh_search_hits and mh_search_first_hits, under the device's lock: the hits of
+// [lower, upper] from `lower` upward, in nonce order, out of windows [cur, cur + w - 1] scanned by
+// the non-stopping hits kernels (hits_scan_range), until `want` entries are collected or `upper` is
+// reached.  w is sized from `spacing`, the nonces per hit the caller observed, for about a quarter
+// of the buffer per window; a window that overflows the buffer all the same is halved and scanned
+// again (one of at most `slots` nonces cannot overflow), one that fits is complete, so sorted and
+// appended.  The last window's entries are all kept: *list may hold more than `want`.
+int hits_window_walk(DevCtx* c, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, uint64_t slots,
+                     uint64_t want, double spacing, std::vector<mh::Hit>* list) {
+    const double per_window = std::max(1.0, (double)slots / 4.0 * spacing);
+    uint64_t w = per_window >= 9.0e18 ? (uint64_t)9.0e18 : (uint64_t)per_window;
+    std::vector<mh::Hit> win;
+    uint64_t cur = lower;
+    list->clear();
+    while (list->size() < want) {
+        const uint64_t hi = (upper - cur < w - 1u) ? upper : cur + (w - 1u);
+        uint64_t wc = 0;
+        const int rc = hits_scan_range(c, pre, cur, hi, target, slots, &wc, &win);
+        if (rc) return rc;
+        if (wc > slots) {  // hi - cur + 1 > slots >= 1 here
+            w = (hi - cur + 1u) / 2u;
+            continue;
+        }
+        std::sort(win.begin(), win.end(), hit_by_nonce);
+        list->insert(list->end(), win.begin(), win.end());
+        if (hi == upper) break;
+        cur = hi + 1u;
+    }
+    return MH_OK;
+}
+
 // mh_search_hits: one scan of the whole range gives the minimum, the exact count (the cursor
 // advances for every hit) and, while the count fits the device buffer, every hit; the host sorts
 // them by nonce and returns the first `cap`.  When the buffer overflowed, which entries it kept
@@ -721,7 +768,7 @@ int hits_scan_range(DevCtx* c, const mh::Prefix& pre, uint64_t lower, uint64_t u
 // scanned by the same kernels: w is sized from the observed density for about a quarter of the
 // buffer per window, a window that overflows all the same is halved and scanned again (one of at
 // most `slots` nonces cannot overflow), one that fits is complete, so sorted and appended, until
-// min(count, cap) entries are collected.  The count and the minimum are the first scan's.
+// min(count, cap) entries are collected (hits_window_walk).  The count and the minimum are the first scan's.
 int search_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, mh_hit* hits,
                      size_t cap, mh_hits* out) {
     DevCtx* c;
@@ -747,31 +794,129 @@ int search_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t up
     out->stored = std::min<uint64_t>(count, cap);
     out->hash = c->h_best->hash;
     out->nonce = c->h_best->nonce;
-    const auto by_nonce = [](const mh::Hit& x, const mh::Hit& y) { return x.nonce < y.nonce; };
     if (cap && count > slots) {  // the buffer dropped entries: rebuild the list window by window
         const double total = (double)(upper - lower) + 1.0;
-        const double per_window = std::max(1.0, (double)slots / 4.0 * (total / (double)count));
-        uint64_t w = per_window >= 9.0e18 ? (uint64_t)9.0e18 : (uint64_t)per_window;
-        std::vector<mh::Hit> list, win;
-        uint64_t cur = lower;
-        while (list.size() < out->stored) {
-            const uint64_t hi = (upper - cur < w - 1u) ? upper : cur + (w - 1u);
-            uint64_t wc = 0;
-            rc = hits_scan_range(c, pre, cur, hi, target, slots, &wc, &win);
-            if (rc) return rc;
-            if (wc > slots) {  // hi - cur + 1 > slots >= 1 here
-                w = (hi - cur + 1u) / 2u;
-                continue;
-            }
-            std::sort(win.begin(), win.end(), by_nonce);
-            list.insert(list.end(), win.begin(), win.end());
-            if (hi == upper) break;
-            cur = hi + 1u;
-        }
+        std::vector<mh::Hit> list;
+        rc = hits_window_walk(c, pre, lower, upper, target, slots, out->stored, total / (double)count, &list);
+        if (rc) return rc;
         if (list.size() < out->stored) return fail(MH_EINTERNAL, "internal: the hit windows hold fewer hits than the scan counted");
         got.swap(list);
     } else {
-        std::sort(got.begin(), got.end(), by_nonce);
+        std::sort(got.begin(), got.end(), hit_by_nonce);
+    }
+    for (uint64_t i = 0; i < out->stored; ++i) hits[i] = mh_hit{got[(size_t)i].hash, got[(size_t)i].nonce};
+    return MH_OK;
+}
+
+// mh_search_first_hits: hits_scan_range's plan, streams, partial flushes and work-queue counters over
+// the stopping hits kernels (hits_stop<J, MODE>, generic_scan_hits_stop; layout.hpp HitsStopArgs),
+// one synchronise, then the k smallest of the appended hits.  Every nonce <= the bound word's final
+// value was hashed (a chunk or tile is only skipped or left above a value the word held, and the
+// word only decreases) and at least k hits are <= it, so the appended hits hold the k smallest of
+// the range whenever they are k or more; with fewer the word was never lowered (it is lowered only
+// from slice counts that hold k appended hits), nothing was skipped and the minimum is the range's.
+// When the device buffer dropped entries, which ones depends on timing: the list is rebuilt from
+// `lower` upward by the window walk of mh_search_hits, on the non-stopping kernels, until k entries
+// are collected or `upper` is reached.
+int search_first_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, mh_hit* hits,
+                           size_t k, mh_first_hits* out) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    if (!c->d_hits) MH_HIP(hipMalloc(&c->d_hits, sizeof(mh::Hit) * MH_HITS_MAX_CAP));
+    if (!c->d_hcursor) MH_HIP(hipMalloc(&c->d_hcursor, sizeof(uint64_t)));
+    if (!c->h_hcursor) MH_HIP(hipHostMalloc(&c->h_hcursor, sizeof(uint64_t), hipHostMallocDefault));
+    if (!c->d_fhits) MH_HIP(hipMalloc(&c->d_fhits, 2 * sizeof(uint64_t)));
+    if (!c->d_slices) MH_HIP(hipMalloc(&c->d_slices, sizeof(uint32_t) * mh::kFirstHitsSlices));
+    if (!c->h_fhits) MH_HIP(hipHostMalloc(&c->h_fhits, sizeof(uint64_t), hipHostMallocDefault));
+#ifdef MH_DEV_HOOKS
+    c->keep = 0;  // mh_search_first_hits refused the hash hooks; nothing of an earlier search's stays
+    c->keep_fast = c->xor_on = c->xor_fast = false;
+#endif
+    const uint64_t slots = hits_slots();
+    const uint64_t total_m1 = upper - lower;  // the range's size minus 1 (its size may be 2^64)
+    MH_HIP(hipMemsetAsync(c->d_best, 0xFF, sizeof(Partial), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_hcursor, 0, sizeof(uint64_t), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_fhits, 0xFF, sizeof(uint64_t), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_fhits + 1, 0, sizeof(uint64_t), c->stream));
+    MH_HIP(hipMemsetAsync(c->d_slices, 0, sizeof(uint32_t) * mh::kFirstHitsSlices, c->stream));
+    const mh::PlanOpts opt = plan_opts();
+    if (opt.queue) MH_HIP(hipMemsetAsync(c->d_counters, 0, sizeof(uint32_t) * kQueueSlots, c->stream));
+    c->qoff = 0;
+    bool any_coarse = false, any_fine = false;
+    if (opt.streams == 2)
+        mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
+            (coarse_piece(p, opt) ? any_coarse : any_fine) = true;
+            return !(any_coarse && any_fine);
+        });
+    const bool split = opt.streams == 2 && any_coarse && any_fine;
+    if (split) {
+        rc = piece_streams_wait_main(c);
+        if (rc) return rc;
+    }
+    const mh::HitsStopArgs hs{mh::HitsArgs{target, (unsigned long long*)c->d_hcursor, c->d_hits, slots},
+                              (uint64_t)k,
+                              (unsigned long long*)c->d_fhits,
+                              c->d_slices,
+                              lower,
+                              total_m1,
+                              mh::first_hits_shift(total_m1),
+                              0u,
+                              (unsigned long long*)(c->d_fhits + 1)};
+    int err = MH_OK;
+    c->poff = 0;
+    c->hits_stop = &hs;
+    mh::plan_search(pre, lower, upper, opt, [&](const mh::Piece& p) {
+        err = enqueue_piece(c, p, opt, split);
+        return err == MH_OK;
+    });
+    c->hits_stop = nullptr;
+    if (!err) err = flush_partials(c, split);
+    if (err) {
+        for (auto ps : c->ps)
+            if (ps) (void)hipStreamSynchronize(ps);
+        (void)hipStreamSynchronize(c->stream);
+        return err;
+    }
+    MH_HIP(hipMemcpyAsync(c->h_best, c->d_best, sizeof(Partial), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_hcursor, c->d_hcursor, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(c->h_fhits, c->d_fhits + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    const uint64_t appended = *c->h_hcursor, scanned = *c->h_fhits;
+    const Partial best = *c->h_best;  // the window walk below reuses the pinned words
+    std::vector<mh::Hit> got;
+    if (appended <= slots) {
+        got.resize((size_t)appended);
+        if (!got.empty()) MH_HIP(hipMemcpy(got.data(), c->d_hits, got.size() * sizeof(mh::Hit), hipMemcpyDeviceToHost));
+        std::sort(got.begin(), got.end(), hit_by_nonce);
+    } else {  // the buffer dropped entries: rebuild the list window by window, from the observed density
+        rc = hits_window_walk(c, pre, lower, upper, target, slots, k, std::max(1.0, (double)scanned) / (double)appended, &got);
+        if (rc) return rc;
+    }
+    out->stored = std::min<uint64_t>(got.size(), k);
+    out->scanned = scanned;
+    if (out->stored < k) {
+        // fewer than k hits: the bound was never lowered, so nothing was skipped
+        if (scanned != total_m1 + 1u)
+            return fail(MH_EINTERNAL, "internal: fewer than k hits, but the scan did not hash the whole range");
+        out->hash = best.hash;
+        out->nonce = best.nonce;
+    } else {
+        out->hash = got[0].hash;
+        out->nonce = got[0].nonce;
+        for (size_t i = 1; i < k; ++i)
+            if (got[i].hash < out->hash || (got[i].hash == out->hash && got[i].nonce < out->nonce)) {
+                out->hash = got[i].hash;
+                out->nonce = got[i].nonce;
+            }
     }
     for (uint64_t i = 0; i < out->stored; ++i) hits[i] = mh_hit{got[(size_t)i].hash, got[(size_t)i].nonce};
     return MH_OK;
@@ -1847,6 +1992,41 @@ int mh_search_hits(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint
     mh::Prefix pre;
     mh::absorb_prefix(msg, len, &pre);
     return search_hits_impl(dev, pre, lower, upper, target, hits, cap, out);
+}
+
+int mh_search_first_hits(int dev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                         mh_hit* hits, size_t k, mh_first_hits* out) {
+    g_err.clear();
+    if (!out) return fail(MH_EINVAL, "NULL output pointer");
+    if (!hits) return fail(MH_EINVAL, "hits is NULL");
+    if (k == 0) return fail(MH_EINVAL, "k is 0");
+    if (k > MH_HITS_MAX_CAP) return fail(MH_EINVAL, "k is larger than MH_HITS_MAX_CAP");
+    int rc = check_common(msg, len);
+    if (rc) return rc;
+    if (lower > upper) return fail(MH_ERANGE, "lower > upper");
+#ifdef MH_DEV_HOOKS
+    // the stopping hits kernels have no variants of these hooks: refuse, never ignore them
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_first_hits does not support ") + hook);
+#endif
+    mh::Prefix pre;
+    mh::absorb_prefix(msg, len, &pre);
+    return search_first_hits_impl(dev, pre, lower, upper, target, hits, k, out);
+}
+
+int mh_first_hits_slices(uint64_t lower, uint64_t upper, uint32_t* shift, uint32_t* slices) {
+    g_err.clear();
+    if (!shift || !slices) return fail(MH_EINVAL, "NULL output pointer");
+    if (lower > upper) return fail(MH_ERANGE, "lower > upper");
+    *shift = mh::first_hits_shift(upper - lower);
+    *slices = mh::first_hits_slices(upper - lower, *shift);
+    return MH_OK;
+}
+
+uint64_t mh_first_hits_bound(uint64_t lower, uint64_t upper, uint64_t k, const uint32_t* counts) {
+    if (!counts || k == 0 || lower > upper) return ~0ull;
+    return mh::first_hits_bound(lower, upper - lower, mh::first_hits_shift(upper - lower), k, counts);
 }
 
 int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,

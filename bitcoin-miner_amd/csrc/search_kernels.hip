@@ -33,6 +33,10 @@
 //                         whose hash is <= a target appended to a device buffer; a third embedded
 //                         code object, loaded by the first such search.
 //   generic_scan_hits     generic_scan for mh_search_hits.
+//   hits_stop<J, MODE>    (fast_search.hip, -DMH_HITS -DMH_STOP) hits_scan for mh_search_first_hits:
+//                         its hits count in slices of the range, its waves publish a bound once the
+//                         slices hold k hits and leave a running chunk that lies above it.
+//   generic_scan_hits_stop  generic_scan_hits for mh_search_first_hits: skipped above the bound.
 //   batch_scan_first      batch_scan for mh_search_first_batch: first-hit keys, per-request device
 //                         words, tiles dispatched in the host's rank-major order.
 //   merge_segments_first  merge_segments, then the winning key back into its hash and the
@@ -100,6 +104,8 @@ extern "C" const unsigned char mh_first_stop_co_begin[];
 extern "C" const unsigned char mh_batch_first_stop_co_begin[];
 // the same source built with -DMH_BATCH -DMH_HITS: batch_hits<J, MODE>, the fused fast pieces of mh_search_hits_batch_ex
 extern "C" const unsigned char mh_batch_hits_co_begin[];
+// the same source built with -DMH_HITS -DMH_STOP: hits_stop<J, MODE>, the fast kernels of mh_search_first_hits
+extern "C" const unsigned char mh_hits_stop_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -245,6 +251,60 @@ __global__ __launch_bounds__(kBlockThreads) void generic_scan_hits(const GenArgs
     }
     block_min(hash, nonce);
     if (threadIdx.x == 0) partials[blockIdx.x] = Partial{hash, nonce};
+}
+
+// generic_scan_hits for mh_search_first_hits (layout.hpp HitsStopArgs): the workgroup
+// is skipped when its first nonce -- its smallest -- lies above the search's bound word (at least k
+// hits of the range are <= the word's value, so none of the tile's nonces is among the k smallest
+// hits); it then writes the sentinel the merge reads and counts nothing.  Otherwise every hit first
+// counts in its slice of the range, lane-parallel, and the counts are back before the wave's lead
+// lane advances the cursor -- whoever gets a cursor value back finds every hit it stands for in the
+// slices -- and the wave whose cursor value plus its own hits reaches k publishes the bound
+// (kernel_common.hpp publish_first_hits_bound).  The workgroup adds its valid nonces to `scanned`.
+// No stop inside a tile.  No test hooks: mh_search_first_hits refuses them.
+__global__ __launch_bounds__(kBlockThreads) void generic_scan_hits_stop(const GenArgs a, Partial* __restrict__ partials,
+                                                                        const HitsStopArgs hs) {
+    using namespace dev;
+    __shared__ uint32_t s_skip;
+    const uint64_t base = a.first + (uint64_t)blockIdx.x * kBlockThreads;  // a valid nonce: blocks = ceil(count / 256)
+    if (threadIdx.x == 0)
+        s_skip = base > __hip_atomic_load(hs.bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
+    __syncthreads();
+    if (s_skip) {  // one value per workgroup
+        if (threadIdx.x == 0) partials[blockIdx.x] = Partial{~0ull, ~0ull};
+        return;
+    }
+    const uint64_t n = base + threadIdx.x;
+    const uint64_t left = a.count - (uint64_t)blockIdx.x * kBlockThreads;  // >= 1
+    uint32_t h0, h1;
+    hash_generic(a, n, h0, h1);
+    uint64_t hash = ((uint64_t)h0 << 32) | h1, nonce = n;
+    const bool hit = threadIdx.x < left && hash <= hs.h.target;
+    const uint64_t hm = __builtin_amdgcn_ballot_w64(hit);
+    if (hm) {  // one value per wave
+        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const uint32_t lead = (uint32_t)__builtin_ctzll(hm);
+        uint32_t back = 0u;
+        if (hit) back = atomicAdd(first_hits_slice(hs, n), 1u);
+        asm volatile("" ::"v"(back) : "memory");  // the slice counts are back before the cursor advances
+        unsigned long long taken = 0ull;
+        if (lane == lead) taken = atomicAdd(hs.h.cursor, (unsigned long long)__builtin_popcountll(hm));
+        const uint64_t first =
+            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(taken >> 32), (int)lead) << 32) |
+            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)taken, (int)lead);
+        const uint64_t slot = first + (uint32_t)__builtin_popcountll(hm & ((1ull << lane) - 1ull));
+        if (hit && slot < hs.h.cap) hs.h.hits[slot] = Hit{hash, nonce};
+        if (first + (uint32_t)__builtin_popcountll(hm) >= hs.k) publish_first_hits_bound(hs, lane);
+    }
+    if (threadIdx.x >= left) {
+        hash = ~0ull;
+        nonce = ~0ull;
+    }
+    block_min(hash, nonce);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = Partial{hash, nonce};
+        atomicAdd(hs.scanned, (unsigned long long)(left < (uint64_t)kBlockThreads ? left : (uint64_t)kBlockThreads));
+    }
 }
 
 // The end of an mh_search_first, one thread on the main stream after the last merge: a winning
@@ -795,8 +855,10 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // parameters and marker
 // or kFastBatchStop, batch_stop<J, MODE> of the eighth (":batch_first_stop"; no hook replaces it):
 // batch_first's parameters, its marker mh_fast_batch_stop_items at sizeof(BatchFirstItem)
+// or kFastHitsStop, hits_stop<J, MODE> of the ninth (":hits_stop"; no hook replaces it): hits_scan's
+// first two parameters, a HitsStopArgs as the third, and fast_search's marker
 enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4, kFastBatchHits = 5,
-                   kFastFirstStop = 6, kFastBatchStop = 7 };
+                   kFastFirstStop = 6, kFastBatchStop = 7, kFastHitsStop = 8 };
 #ifdef MH_DEV_HOOKS
 std::string batch_module_path() {
     const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
@@ -809,13 +871,13 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                          FastVariant variant = kFastProduct) {
     const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
     const bool bfirst = variant == kFastBatchFirst, bhits = variant == kFastBatchHits, fstop = variant == kFastFirstStop;
-    const bool bstop = variant == kFastBatchStop;
+    const bool bstop = variant == kFastBatchStop, hstop = variant == kFastHitsStop;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
-    const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : batch ? batch_module_path()
+    const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : hstop ? ":hits_stop" : batch ? batch_module_path()
                              : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : (co && *co) ? co : "";
 #else
-    const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : batch ? batch_module_path()
+    const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : hstop ? ":hits_stop" : batch ? batch_module_path()
                              : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
@@ -825,6 +887,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
         const hipError_t e = first          ? hipModuleLoadData(&m, mh_first_co_begin)
                              : fstop        ? hipModuleLoadData(&m, mh_first_stop_co_begin)
                              : hits         ? hipModuleLoadData(&m, mh_hits_co_begin)
+                             : hstop        ? hipModuleLoadData(&m, mh_hits_stop_co_begin)
                              : path == ":batch" ? hipModuleLoadData(&m, mh_batch_co_begin)
                              : bfirst       ? hipModuleLoadData(&m, mh_batch_first_co_begin)
                              : bstop        ? hipModuleLoadData(&m, mh_batch_first_stop_co_begin)
@@ -874,6 +937,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                  : first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : fstop ? "_ZN2mh9stop_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
+                 : hstop ? "_ZN2mh9hits_stopILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_12HitsStopArgsE"
                  : batch ? "_ZN2mh10batch_fastILi%dELi%dEEEvPKNS_13BatchFastItemEPKjPNS_7PartialE"
                         : "_ZN2mh11fast_searchILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialE",
                  J, mode);
@@ -1043,6 +1107,20 @@ hipError_t launch_fast_hits(int dev, int J, int mode, const FastArgs& a, Partial
                             hipStream_t s) {
     HitsArgs ha = h;
     return launch_fast_variant(dev, J, mode, a, partials, kFastHits, &ha, s);
+}
+
+// mh_search_first_hits: hits_stop<J, mode> of the stopping hits code object (loaded on dev by the
+// first such call), h as the third kernel parameter.
+hipError_t launch_fast_hits_stop(int dev, int J, int mode, const FastArgs& a, Partial* partials, const HitsStopArgs& h,
+                                 hipStream_t s) {
+    HitsStopArgs ha = h;
+    return launch_fast_variant(dev, J, mode, a, partials, kFastHitsStop, &ha, s);
+}
+
+hipError_t launch_generic_scan_hits_stop(const GenArgs& a, Partial* partials, uint32_t blocks, const HitsStopArgs& h,
+                                         hipStream_t s) {
+    hipLaunchKernelGGL(generic_scan_hits_stop, dim3(blocks), dim3(kBlockThreads), 0, s, a, partials, h);
+    return hipGetLastError();
 }
 
 hipError_t launch_generic_scan_hits(const GenArgs& a, Partial* partials, uint32_t blocks, const HitsArgs& h,

@@ -13,6 +13,8 @@ tests read like the reference (line numbers into the reference repo):
                              the smallest nonce whose hash is <= target
   search_hits(msg, lower, upper, target, cap=4096)
                              every nonce whose hash is <= target, and how many there are
+  search_first_hits(msg, lower, upper, target, k)
+                             the k smallest nonces whose hash is <= target, without the full scan
   search_first_batch(requests)
                              many small first-hit searches fused into one GPU pass
                              (fuse_fast=True: the fast pieces of larger ones too)
@@ -39,7 +41,7 @@ from ._lib import MH_ENOTREQ, MH_EINTERNAL, MH_EREJECTED  # noqa: F401
 from ._lib import mh_request, mh_result, mh_batch_item, mh_first  # noqa: F401
 from ._lib import mh_batch_piece, MH_BATCH_FUSE_FAST, MH_BATCH_FAST_MAX_NONCES  # noqa: F401
 from ._lib import mh_first_request, mh_first_result, MH_FIRST_STOP_RUNNING  # noqa: F401
-from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP  # noqa: F401
+from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP, mh_first_hits  # noqa: F401
 from ._lib import mh_hits_request, mh_hits_result, mh_hits_region  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
@@ -99,6 +101,21 @@ def search_hits(msg, lower, upper, target, cap=4096, dev=0):
     out = mh_hits()
     _check(lib.mh_search_hits(dev, m, len(m), lower, upper, target, buf, cap, ctypes.byref(out)))
     return out.count, [(buf[i].nonce, buf[i].hash) for i in range(out.stored)], (out.hash, out.nonce)
+
+
+def search_first_hits(msg, lower, upper, target, k, dev=0):
+    """([(nonce, hash), ...], (hash, nonce), scanned): the min(k, count) smallest nonces n of [lower,
+    upper] with Hash(msg, n) <= target in increasing order with their hashes -- search_hits' first
+    entries -- from kernels that stop once k of them are known (mh_search_first_hits); (hash, nonce)
+    is search()'s result for the range when fewer than k qualify, else the minimum of the k entries;
+    scanned is how many nonces of the range were hashed."""
+    m = _b(msg)
+    if k < 1 or k > MH_HITS_MAX_CAP:
+        raise MinehipError(MH_EINVAL, f"k must be 1..{MH_HITS_MAX_CAP}")
+    buf = (mh_hit * k)()
+    out = mh_first_hits()
+    _check(lib.mh_search_first_hits(dev, m, len(m), lower, upper, target, buf, k, ctypes.byref(out)))
+    return [(buf[i].nonce, buf[i].hash) for i in range(out.stored)], (out.hash, out.nonce), out.scanned
 
 
 def search_multi(msg, lower, upper, devs=None, chunk=0):

@@ -43,6 +43,7 @@ EXPORTS = (
     "mh_search_hits_batch", "mh_hits_batch_regions", "mh_search_batch_ex", "mh_batch_plan_ex",
     "mh_search_first_batch_ex", "mh_first_batch_order_ex", "mh_search_hits_batch_ex", "mh_hits_batch_regions_ex",
     "mh_miner_handle_batch_ex", "mh_search_first_ex", "mh_search_first_batch_stop",
+    "mh_search_first_hits", "mh_first_hits_slices", "mh_first_hits_bound",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -92,6 +93,11 @@ class mh_hit(ctypes.Structure):
 
 class mh_hits(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("stored", ctypes.c_uint64), ("hash", ctypes.c_uint64),
+                ("nonce", ctypes.c_uint64)]
+
+
+class mh_first_hits(ctypes.Structure):
+    _fields_ = [("stored", ctypes.c_uint64), ("scanned", ctypes.c_uint64), ("hash", ctypes.c_uint64),
                 ("nonce", ctypes.c_uint64)]
 
 
@@ -215,6 +221,10 @@ def _load():
                                              ctypes.POINTER(mh_first_result)]
     L.mh_first_batch_order_ex.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.c_uint32, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64]
+    L.mh_search_first_hits.argtypes = [ctypes.c_int, u8p, sz, u64, u64, u64, ctypes.POINTER(mh_hit), sz,
+                                       ctypes.POINTER(mh_first_hits)]
+    L.mh_first_hits_slices.argtypes = [u64, u64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    L.mh_first_hits_bound.argtypes = [u64, u64, u64, ctypes.POINTER(ctypes.c_uint32)]
     L.mh_search_hits_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hit), sz,
                                        ctypes.POINTER(mh_hits_result)]
     L.mh_search_hits_batch_ex.argtypes = [ctypes.c_int, ctypes.POINTER(mh_hits_request), sz, ctypes.c_uint32,
@@ -262,7 +272,7 @@ def _load():
                "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
                "mh_sched_create_ex": vp, "mh_server_create_ex": vp, "mh_sched_default_queue_opts": None,
-               "mh_sched_miner_queue": i64,
+               "mh_sched_miner_queue": i64, "mh_first_hits_bound": u64,
                "mh_sched_destroy": None, "mh_server_destroy": None}
     for name in EXPORTS:
         getattr(L, name).restype = restype.get(name, ctypes.c_int)

@@ -86,6 +86,15 @@ def batch_hits_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def hits_stop_code_object():
+    """The embedded code object of the stopping hits kernels (mh_search_first_hits):
+    hits_stop<J, MODE>, fast_search.hip built with -DMH_HITS -DMH_STOP
+    (mh_hits_stop_co_begin .. mh_hits_stop_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_hits_stop_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_hits_stop_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def unpack_msgpack(b):
     """Decode one MessagePack object (the subset AMDGPU metadata uses: maps, arrays, strings,
     binary, integers, floats, booleans, nil).  No dependency on the msgpack package."""
@@ -201,6 +210,11 @@ def first_stop_kernel_resources():
 def hits_kernel_resources():
     """The same of the embedded hits_scan<J, MODE> kernels."""
     return fast_kernel_resources(hits_code_object(), r"_ZN2mh9hits_scanILi(\d+)ELi(\d+)E")
+
+
+def hits_stop_kernel_resources():
+    """The same of the embedded hits_stop<J, MODE> kernels."""
+    return fast_kernel_resources(hits_stop_code_object(), r"_ZN2mh9hits_stopILi(\d+)ELi(\d+)E")
 
 
 def batch_kernel_resources(co=None):

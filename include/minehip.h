@@ -307,6 +307,51 @@ typedef struct mh_hits {
 int mh_search_hits(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                    uint64_t target, mh_hit *hits, size_t cap, mh_hits *out);
 
+/* ---- the first k hits: the k smallest qualifying nonces, without the full scan ---- */
+
+typedef struct mh_first_hits {
+    uint64_t stored;      /* entries written to hits: min(k, qualifying nonces of the range) */
+    uint64_t scanned;     /* nonces of [lower, upper] actually hashed */
+    uint64_t hash, nonce; /* stored < k: exactly what mh_search returns for the range;
+                             stored == k: the lexicographic minimum (hash, nonce) of the k entries */
+} mh_first_hits; /* 32 bytes */
+
+/* The first k nonces of [lower, upper] with Hash(msg, n) <= target -- what a share collector asks --
+ * between mh_search_first (k = 1, stops early) and mh_search_hits (every hit, never stops early).
+ * hits[0 .. out->stored) are the `stored` smallest such nonces in strictly increasing nonce order,
+ * each with its hash: bit for bit the first `stored` entries mh_search_hits(..., cap = k) returns.
+ * stored, the entries, hash and nonce never depend on the launch plan, the streams, the queue mode,
+ * the timing or MINEHIP_HITS_SLOTS; only `scanned` does.  With stored < k the whole range was
+ * hashed: scanned == upper - lower + 1 and hash / nonce are mh_search's.  With stored == k,
+ * hits[k-1].nonce - lower + 1 <= scanned <= upper - lower + 1.  Hence with k == 1, stored, hash and
+ * nonce equal mh_search_first's found, hash and nonce; with k >= count, stored, the entries, hash
+ * and nonce equal mh_search_hits' count, entries and minimum.
+ * The scan kernels are mh_search_hits' with one device word per search, the bound: every hit that is
+ * appended also counts in one of at most 1,024 slices of the range (mh_first_hits_slices), and once
+ * the slices hold k hits the end of the slice where the prefix sum reaches k is published
+ * (mh_first_hits_bound), only ever lowered: at least k qualifying nonces are <= it, so a chunk or
+ * tile wholly above it is skipped and a running chunk is left at its next group of ten nonces.
+ * Nothing waits on the word; a stale read only stops later.  If the device hit buffer
+ * (MH_HITS_MAX_CAP entries, MINEHIP_HITS_SLOTS) overflowed, the list is rebuilt from `lower` upward
+ * by mh_search_hits' window walk until k entries are collected.
+ * Errors, before any device is touched: MH_EINVAL for out == NULL, hits == NULL, k == 0 or
+ * k > MH_HITS_MAX_CAP; MH_ERANGE, MH_ETOOLONG and MH_EINVAL for a NULL msg with len > 0, as
+ * mh_search; then MH_ENODEV.  The dev build refuses the hash and code-object hooks as
+ * mh_search_hits does.  One device only, no batched form, nothing in the LSP protocol or the miner.
+ * Additive in ABI 5 (no existing struct or function changes). */
+int mh_search_first_hits(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
+                         uint64_t target, mh_hit *hits, size_t k, mh_first_hits *out);
+
+/* Host only: shift and slice count (<= 1024) mh_search_first_hits uses for [lower, upper]: slices of
+ * 2^shift nonces, shift the smallest value with 1024 << shift >= upper - lower + 1.  MH_EINVAL for a
+ * NULL pointer, MH_ERANGE for lower > upper. */
+int mh_first_hits_slices(uint64_t lower, uint64_t upper, uint32_t *shift, uint32_t *slices);
+/* Host only: the value the kernels publish from these slice counts (counts[s]: hits counted in
+ * slice s, nonces lower + (s << shift) ..): lower + min(upper - lower, ((s + 1) << shift) - 1) for
+ * the first slice s whose prefix sum is >= k; 2^64-1 while the counts sum to < k (or for a NULL
+ * pointer, k == 0 or lower > upper). */
+uint64_t mh_first_hits_bound(uint64_t lower, uint64_t upper, uint64_t k, const uint32_t *counts);
+
 /* ---- batched hits: every hit of many small Requests in one pass ----------- */
 
 typedef struct mh_hits_request {
