@@ -33,9 +33,11 @@ FASTFLAGS ?=
 # and the stopping first-hit kernels stop_scan<J, MODE> of mh_search_first_ex (-DMH_FIRST -DMH_STOP,
 # DESIGN.md §3; embedded too, no test variant) and the stopping first-hit batch kernels
 # batch_stop<J, MODE> of mh_search_first_batch_stop (-DMH_BATCH -DMH_FIRST -DMH_STOP; likewise) and the
-# stopping hits kernels hits_stop<J, MODE> of mh_search_first_hits (-DMH_HITS -DMH_STOP; likewise)
+# stopping hits kernels hits_stop<J, MODE> of mh_search_first_hits (-DMH_HITS -DMH_STOP; likewise) and the
+# stopping hits batch kernels batch_bound<J, MODE> of mh_search_first_hits_batch (-DMH_BATCH -DMH_HITS
+# -DMH_STOP; likewise)
 FAST_NAMES := fast_search fast_search_keep fast_first fast_hits fast_batch fast_batch_keep fast_batch_first fast_batch_hits \
-              fast_first_stop fast_batch_first_stop fast_hits_stop
+              fast_first_stop fast_batch_first_stop fast_hits_stop fast_batch_bound
 FASTFLAGS_fast_search_keep := -DMH_HASH_KEEP
 FASTFLAGS_fast_first := -DMH_FIRST
 FASTFLAGS_fast_hits := -DMH_HITS
@@ -46,6 +48,7 @@ FASTFLAGS_fast_batch_hits := -DMH_BATCH -DMH_HITS
 FASTFLAGS_fast_first_stop := -DMH_FIRST -DMH_STOP
 FASTFLAGS_fast_batch_first_stop := -DMH_BATCH -DMH_FIRST -DMH_STOP
 FASTFLAGS_fast_hits_stop := -DMH_HITS -DMH_STOP
+FASTFLAGS_fast_batch_bound := -DMH_BATCH -DMH_HITS -DMH_STOP
 FIRST_CO := $(BUILD)/fast_first.hsaco
 HITS_CO := $(BUILD)/fast_hits.hsaco
 BATCH_CO := $(BUILD)/fast_batch.hsaco
@@ -54,6 +57,7 @@ BATCH_HITS_CO := $(BUILD)/fast_batch_hits.hsaco
 FIRST_STOP_CO := $(BUILD)/fast_first_stop.hsaco
 BATCH_FIRST_STOP_CO := $(BUILD)/fast_batch_first_stop.hsaco
 HITS_STOP_CO := $(BUILD)/fast_hits_stop.hsaco
+BATCH_BOUND_CO := $(BUILD)/fast_batch_bound.hsaco
 
 LSPLIB  := $(PKG)/minehip/liblsp440.so
 APPS    := $(CSRC)/apps
@@ -110,9 +114,10 @@ ADD3_LIKE_fast_batch_hits := $(FAST_SP)
 ADD3_LIKE_fast_first_stop := $(FAST_SP)
 ADD3_LIKE_fast_batch_first_stop := $(FAST_SP)
 ADD3_LIKE_fast_hits_stop := $(FAST_SP)
+ADD3_LIKE_fast_batch_bound := $(FAST_SP)
 $(BUILD)/fast_first_split.s $(BUILD)/fast_hits_split.s $(BUILD)/fast_batch_split.s $(BUILD)/fast_batch_keep_split.s \
 $(BUILD)/fast_batch_first_split.s $(BUILD)/fast_batch_hits_split.s $(BUILD)/fast_first_stop_split.s \
-$(BUILD)/fast_batch_first_stop_split.s $(BUILD)/fast_hits_stop_split.s: $(FAST_SP) $(CSRC)/loop_mix.py
+$(BUILD)/fast_batch_first_stop_split.s $(BUILD)/fast_hits_stop_split.s $(BUILD)/fast_batch_bound_split.s: $(FAST_SP) $(CSRC)/loop_mix.py
 $(FAST_NAMES:%=$(BUILD)/%_prio.s): $(BUILD)/%_prio.s: $(BUILD)/%_split.s $(CSRC)/issue_prio.py $(CSRC)/valu_rates.py
 	python3 $(CSRC)/issue_prio.py $< $@
 $(FAST_MIX): $(FAST_PS) $(CSRC)/loop_mix.py $(CSRC)/valu_rates.py
@@ -128,7 +133,7 @@ $(BUILD)/fast_search_nomarker.hsaco: $(FAST_PS)
 	$(LLVM)/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=$(ARCH) -c -o $(BUILD)/fast_search_nomarker.o $(BUILD)/fast_search_nomarker.s
 	$(LLVM)/ld.lld -shared -o $@ $(BUILD)/fast_search_nomarker.o
 $(FAST_O): $(CSRC)/fast_co.S $(FAST_CO) $(FIRST_CO) $(HITS_CO) $(BATCH_CO) $(BATCH_FIRST_CO) $(BATCH_HITS_CO) $(FIRST_STOP_CO) \
-           $(BATCH_FIRST_STOP_CO) $(HITS_STOP_CO)
+           $(BATCH_FIRST_STOP_CO) $(HITS_STOP_CO) $(BATCH_BOUND_CO)
 	gcc -c -fPIC -Wa,-I,$(BUILD) -o $@ $<
 
 # native C++ callers of the C-ABI (rpath: the library next to the package)

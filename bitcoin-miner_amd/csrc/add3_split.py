@@ -52,8 +52,9 @@ def split_line(m):
 # or hits_scan<J, MODE> of the -DMH_HITS build or batch_fast<J, MODE> of the -DMH_BATCH builds or
 # batch_first<J, MODE> of the -DMH_BATCH -DMH_FIRST build or batch_hits<J, MODE> of the -DMH_BATCH
 # -DMH_HITS build or stop_scan<J, MODE> of the -DMH_FIRST -DMH_STOP build or batch_stop<J, MODE> of
-# the -DMH_BATCH -DMH_FIRST -DMH_STOP build or hits_stop<J, MODE> of the -DMH_HITS -DMH_STOP build
-KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits|9stop_scan|10batch_stop|9hits_stop)\S*:")
+# the -DMH_BATCH -DMH_FIRST -DMH_STOP build or hits_stop<J, MODE> of the -DMH_HITS -DMH_STOP build or
+# batch_bound<J, MODE> of the -DMH_BATCH -DMH_HITS -DMH_STOP build
+KERNEL = re.compile(r"^_ZN2mh(?:11fast_search|10first_scan|9hits_scan|10batch_fast|11batch_first|10batch_hits|9stop_scan|10batch_stop|9hits_stop|11batch_bound)\S*:")
 
 
 def split(text, k, pattern=None, phase=None):
@@ -148,9 +149,9 @@ def loop_add3(text):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import loop_mix
     bodies = loop_mix.kernels(text)
-    # batch_first and batch_stop exit early (a skipped chunk): their loops lie behind the first s_endpgm
+    # batch_first, batch_stop and batch_bound exit early (a skipped chunk): their loops lie behind the first s_endpgm
     bodies.update({name: body for name, body in loop_mix.kernels(text, whole=True).items()
-                   if loop_mix.BATCH_FIRST.match(name) or loop_mix.BATCH_STOP.match(name)})
+                   if loop_mix.BATCH_FIRST.match(name) or loop_mix.BATCH_STOP.match(name) or loop_mix.BATCH_BOUND.match(name)})
     return {name: sum(o == "v_add3_u32" for o in loop_mix.per_nonce_loop(body))
             for name, body in bodies.items() if KERNEL.match(name + ":")}
 

@@ -19,7 +19,10 @@
    build/fast_batch_first_stop.hsaco), loaded per device by the first such
    call that fuses a fast piece, and the stopping hits kernels of
    mh_search_first_hits (-DMH_HITS -DMH_STOP, build/fast_hits_stop.hsaco),
-   loaded per device by the first such call. */
+   loaded per device by the first such call, and the stopping hits batch
+   kernels of mh_search_first_hits_batch (-DMH_BATCH -DMH_HITS -DMH_STOP,
+   build/fast_batch_bound.hsaco), loaded per device by the first such call
+   that fuses a fast piece. */
     .section .rodata
     .p2align 12
     .globl mh_fast_co_begin
@@ -93,4 +96,12 @@ mh_hits_stop_co_begin:
     .globl mh_hits_stop_co_end
 mh_hits_stop_co_end:
     .size mh_hits_stop_co_begin, mh_hits_stop_co_end - mh_hits_stop_co_begin
+    .p2align 12
+    .globl mh_batch_bound_co_begin
+    .type mh_batch_bound_co_begin, @object
+mh_batch_bound_co_begin:
+    .incbin "fast_batch_bound.hsaco"
+    .globl mh_batch_bound_co_end
+mh_batch_bound_co_end:
+    .size mh_batch_bound_co_begin, mh_batch_bound_co_end - mh_batch_bound_co_begin
     .section .note.GNU-stack,"",@progbits

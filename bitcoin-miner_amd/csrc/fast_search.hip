@@ -43,6 +43,10 @@
 // DESIGN.md §3): hits_scan whose hits also count in slices of the range, whose waves publish a bound
 // once the slices hold k hits and leave a running chunk that lies wholly above it, a ninth embedded
 // code object that mh_search_first_hits loads; likewise (everything of it sits under MH_HITS and MH_STOP).
+// -DMH_BATCH -DMH_HITS -DMH_STOP builds batch_bound<J, MODE> (build/fast_batch_bound.hsaco, through the
+// same passes): batch_first's table, order and grid around that stopping hits chunk body,
+// which reaches its request's words through the item, a tenth embedded code object that
+// mh_search_first_hits_batch loads; likewise (everything of it sits under MH_HITS and MH_STOP).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -69,6 +73,15 @@ constexpr int min_waves(int J, int MODE) {
 #ifdef MH_MIN_WAVES
     return MH_MIN_WAVES;
 #else
+#ifdef MH_BATCH
+#ifdef MH_HITS
+#ifdef MH_STOP
+    // batch_bound<0, OneEarly>: hits_stop's kernel of the layout takes 64 VGPRs, 8 waves; left at the
+    // Early budget of 7 this build took 65
+    if (J == 0 && MODE == 3 && !MH_ONEPRE_WAVES) return 8;
+#endif
+#endif
+#endif
     return (MH_ONEPRE_WAVES && MODE % 3 != 2) ? MH_ONEPRE_WAVES
          : (MODE == 3 || MODE == 4) ? MH_EARLY_WAVES
          : MODE % 3 == 2 ? 4
@@ -414,7 +427,16 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
         // nor the floor is held across the per-nonce loop.  A poll, never a wait.
         {
             using KHStop = __attribute__((address_space(4))) const HitsStopKernArgs;
+#ifdef MH_BATCH
+            // batch_bound: the kernarg segment holds the launch's four table pointers, so the word's
+            // address and the floor's terms come from the item `a` heads (layout.hpp BatchBoundItem:
+            // FastArgs and HitsStopArgs where HitsStopKernArgs has them), through a copy of the item's
+            // address laundered here for the same reason.  The word and the floor are this request's
+            // and this piece's.
+            KHStop* kb = (KHStop*)&a;
+#else
             KHStop* kb = (KHStop*)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
             asm volatile("" : "+s"(kb));
             const HitsStopKernArgs& bk = *(const HitsStopKernArgs*)kb;
             const uint64_t seen = __hip_atomic_load(bk.h.bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -481,8 +503,10 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
             }
 #endif
 #ifdef MH_HITS
+#ifndef MH_BATCH
         // hits_stop: likewise (its group loop holds the poll's break; left to the compiler, ten
-        // One and Pre layouts redo one to four of these adds on every nonce)
+        // One and Pre layouts redo one to four of these adds on every nonce; with MH_BATCH the
+        // block above has made them)
         uint32_t kwg[64];
 #pragma unroll
         for (int t = 16; t < (BM == kModeTwo ? 64 : 63); ++t)
@@ -490,6 +514,7 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                 kwg[t] = K[t] + wg[t];
                 asm volatile("" : "+v"(kwg[t]));
             }
+#endif
 #endif
 #endif
         // round J-1 reads the group-level word J-1 (Early: it is run-level, done above)
@@ -506,7 +531,9 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
         const uint32_t aJ = t1J + t2J, eJ = gd + t1J;
 #endif
 #ifdef MH_HITS
-        const uint32_t aJ = t1J + t2J, eJ = gd + t1J;  // hits_stop: likewise
+#ifndef MH_BATCH
+        const uint32_t aJ = t1J + t2J, eJ = gd + t1J;  // hits_stop: likewise (with MH_BATCH: made above)
+#endif
 #endif
 #endif
 
@@ -662,7 +689,11 @@ __device__ __forceinline__ void fast_chunk(const FastArgs& a, Partial* __restric
                         // through `a` they are loaded ahead of the loops and held in SGPRs across the
                         // per-nonce loop, which costs the Two layouts' loops three to six v_readlane_b32)
                         using KHits2 = __attribute__((address_space(4))) const HitsStopKernArgs;
+#ifdef MH_BATCH
+                        KHits2* kq = (KHits2*)&a;  // batch_bound: the item's, as the poll's
+#else
                         KHits2* kq = (KHits2*)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
                         asm volatile("" : "+s"(kq));
                         const HitsStopArgs& hs = ((const HitsStopKernArgs*)kq)->h;
                         {
@@ -911,6 +942,58 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_first
 }
 #else
 #ifdef MH_HITS
+#ifdef MH_STOP
+// ---------------------------------------------------------------------------
+// batch_bound<J, MODE>: the fast pieces of many first-k-hits requests in one launch,
+// for mh_search_first_hits_batch(MH_BATCH_FUSE_FAST)
+// ---------------------------------------------------------------------------
+// batch_first's wrapper -- a static grid, workgroup b runs chunk order[b] of the launch, the host's
+// dispatch order, of the item chunk_item[order[b]] names -- around hits_stop's chunk body (layout.hpp
+// BatchBoundItem: the request's HitsStopArgs sit where hits_stop's kernarg segment holds them, and
+// the body reaches them through the item).  Before any hashing thread 0 reads the request's bound
+// word once: a chunk all of whose nonces are larger (hits_floor, attained, so exact) writes the
+// sentinel and ends; otherwise the chunk runs, its waves count what they hash, poll the word once
+// per group of ten nonces and leave the chunk once it lies above the word.  The word, the cursor,
+// the region and the slice counters of an item are its request's -- the words the request's generic
+// tiles (batch_scan_bound) use -- so a request's bound stops that request's chunks and no other's.
+// The word only decreases, and whenever it holds B at least k hits of the request are <= B, so no
+// chunk holding one of the request's k smallest hits is skipped or left whatever value a read
+// returns: a stale read only skips less (claim_below_bound's argument, per request).  Nothing waits
+// on a word, every workgroup that runs reaches block_min and its barriers: the grid always drains.
+static_assert(__builtin_offsetof(BatchBoundItem, h) == __builtin_offsetof(HitsStopKernArgs, h) &&
+                  __builtin_offsetof(BatchBoundItem, args) == 0,
+              "the chunk body finds an item's HitsStopArgs where hits_stop's kernarg segment holds them");
+template <int J, int MODE>
+__global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_bound(const BatchBoundItem* __restrict__ items,
+                                                                           const uint32_t* __restrict__ chunk_item,
+                                                                           const uint32_t* __restrict__ order,
+                                                                           Partial* __restrict__ partials) {
+    using KItem = __attribute__((address_space(4))) const BatchBoundItem;
+    __shared__ uint32_t s_skip;
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[blockIdx.x]);
+    const uint32_t ii = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk_item[c]);
+    KItem* k = (KItem*)(items + ii);
+    asm volatile("" : "+s"(k));
+    const uint32_t blk = c - k->chunk0, slot0 = k->slot0;
+    if (threadIdx.x == 0) {
+        const FastArgs& a = ((const BatchBoundItem*)k)->args;
+        const HitsStopArgs& h = ((const BatchBoundItem*)k)->h;
+        const uint64_t seen = __hip_atomic_load(h.bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t skip = 0u;
+        if (hits_floor<MODE>(a, blk) > seen) {
+            uint64_t ones = ~0ull;
+            asm volatile("" : "+v"(ones));  // made here, as claim_below_bound's
+            partials[slot0 + blk] = Partial{ones, ones};
+            skip = 1u;
+        }
+        s_skip = skip;
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(s_skip)) return;  // one value per workgroup: scalar
+    asm volatile("" : "+s"(k));
+    fast_chunk<J, MODE>(((const BatchBoundItem*)k)->args, partials + slot0, blk);
+}
+#else
 // ---------------------------------------------------------------------------
 // batch_hits<J, MODE>: the fast pieces of many hits requests in one launch, for
 // mh_search_hits_batch_ex(MH_BATCH_FUSE_FAST)
@@ -941,6 +1024,7 @@ __global__ __launch_bounds__(kBlockThreads, min_waves(J, MODE)) void batch_hits(
     asm volatile("" : "+s"(k));
     fast_chunk<J, MODE>(((const BatchHitsItem*)k)->args, partials + slot0, b - chunk0);
 }
+#endif  // MH_STOP
 #else
 // ---------------------------------------------------------------------------
 // batch_fast<J, MODE>: the fast pieces of many requests in one launch, for
@@ -1162,9 +1246,15 @@ __device__ __attribute__((used)) uint8_t mh_fast_batch_first_items[sizeof(BatchF
 #endif
 #else
 #ifdef MH_HITS
+#ifdef MH_STOP
+// Marker of the first-k-hits batch code object instead: its kernels read BatchBoundItems of this size
+// (the library launches batch_bound only from a code object that carries it, search_kernels.hip).
+__device__ __attribute__((used)) uint8_t mh_fast_batch_bound_items[sizeof(BatchBoundItem)];
+#else
 // Marker of the hits batch code object instead: its kernels read BatchHitsItems of this size (the
 // library launches batch_hits only from a code object that carries it, search_kernels.hip).
 __device__ __attribute__((used)) uint8_t mh_fast_batch_hits_items[sizeof(BatchHitsItem)];
+#endif
 #else
 // Marker of the batch code object instead: its kernels read BatchFastItems of this size (the
 // library launches batch_fast only from a code object that carries it, search_kernels.hip).
@@ -1201,9 +1291,15 @@ __device__ __attribute__((used)) uint8_t mh_fast_hash_keep[sizeof(FastArgs)];
 #endif
 #else
 #ifdef MH_HITS
+#ifdef MH_STOP
+#define MH_INST(j, m) \
+    template __global__ void batch_bound<j, m>(const BatchBoundItem* __restrict__, const uint32_t* __restrict__, \
+                                               const uint32_t* __restrict__, Partial* __restrict__);
+#else
 #define MH_INST(j, m) \
     template __global__ void batch_hits<j, m>(const BatchHitsItem* __restrict__, const uint32_t* __restrict__, \
                                               Partial* __restrict__);
+#endif
 #else
 #define MH_INST(j, m) \
     template __global__ void batch_fast<j, m>(const BatchFastItem* __restrict__, const uint32_t* __restrict__, \

@@ -320,4 +320,52 @@ struct BatchHitsItem {
 };
 static_assert(sizeof(BatchHitsItem) % 16 == 0, "items are laid out back to back in the pass's tables");
 
+// ---- batched first k hits (batch_scan_bound / merge_segments_bound) ----
+// The device words of one request of a pass of mh_search_first_hits_batch, in a table parallel to
+// the segments, found by a tile through entry_req[entry] as BatchHitsWords are: BatchHitsWords'
+// four (the append through `cursor` into the request's region), the request's k, its bound word
+// (all ones at the start, only ever lowered: whenever it holds B < 2^64-1, at least k hits of the
+// request are <= B), the range its slices cut (layout.hpp first_hits_shift / first_hits_slices of
+// the request's own range) and the count of nonces hashed.  The request's kFirstHitsSlices slice
+// counters sit at slices + request * kFirstHitsSlices of a buffer of the pass's own, zeroed before
+// the pass.  cursor, bound and scanned are written on the device; the initial values (cursor = 0,
+// bound = all ones, scanned = 0) travel in the pass's table copy.
+struct BatchBoundWords {
+    uint64_t target;
+    unsigned long long cursor;
+    uint64_t offset;
+    uint64_t slots;
+    uint64_t k;
+    unsigned long long bound;
+    uint64_t lower;
+    uint64_t span;                // upper - lower
+    uint32_t shift;
+    uint32_t pad_;                // 0
+    unsigned long long scanned;
+};
+static_assert(sizeof(BatchBoundWords) % 16 == 0, "the words are laid out back to back in the pass's tables");
+
+// One request's result of a pass, as merge_segments_bound writes it and the host copies it back.
+struct BatchBoundResult {
+    uint64_t hash, nonce, count, scanned;
+};
+
+// ---- fused fast pieces of such a batch (batch_bound<J, MODE> of build/fast_batch_bound.hsaco) ----
+// One fast piece of one request of a pass of mh_search_first_hits_batch(MH_BATCH_FUSE_FAST): a
+// BatchFastItem with the request's parameters where hits_stop's kernarg segment holds them -- a
+// HitsStopArgs one pointer behind FastArgs -- so the chunk body reaches them through the item as it
+// reaches them through the kernarg segment there.  The host fills in the pointers once it knows
+// where the pass's tables go: cursor, bound and scanned are the device addresses of the request's
+// BatchBoundWords, h.h.hits and h.h.cap the request's region, h.slices the request's counters: the
+// words its generic tiles use.  Workgroup b of the launch runs chunk order[b] - chunk0 of the item
+// chunk_item[order[b]] names and writes partials[slot0 + that chunk].
+struct BatchBoundItem {
+    FastArgs args;
+    Partial* unused;      // null; where hits_stop's partials parameter sits
+    HitsStopArgs h;
+    uint32_t chunk0;      // first chunk of the item in its launch
+    uint32_t slot0;       // first partial slot of the item in its pass
+};
+static_assert(sizeof(BatchBoundItem) % 16 == 0, "items are laid out back to back in the pass's tables");
+
 }  // namespace mh

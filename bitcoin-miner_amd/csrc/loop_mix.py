@@ -68,6 +68,8 @@ STOP = re.compile(r"^_ZN2mh9stop_scanILi(\d+)ELi(\d+)EE")  # the -DMH_FIRST -DMH
 # the -DMH_BATCH -DMH_FIRST -DMH_STOP build's kernels (build/fast_batch_first_stop_prio.s); whole=True, as batch_first's
 BATCH_STOP = re.compile(r"^_ZN2mh10batch_stopILi(\d+)ELi(\d+)EE")
 HITS_STOP = re.compile(r"^_ZN2mh9hits_stopILi(\d+)ELi(\d+)EE")  # the -DMH_HITS -DMH_STOP build's kernels (build/fast_hits_stop_prio.s)
+# the -DMH_BATCH -DMH_HITS -DMH_STOP build's kernels (build/fast_batch_bound_prio.s); whole=True, as batch_first's
+BATCH_BOUND = re.compile(r"^_ZN2mh11batch_boundILi(\d+)ELi(\d+)EE")
 BATCH_HITS = re.compile(r"^_ZN2mh10batch_hitsILi(\d+)ELi(\d+)EE")  # the -DMH_BATCH -DMH_HITS build's kernels (build/fast_batch_hits_prio.s)
 
 

@@ -91,6 +91,15 @@ hipError_t launch_batch_scan_hits_slots(const BatchEntry* entries, const uint32_
                                         hipStream_t s);
 hipError_t launch_batch_hits(int dev, int J, int mode, const BatchHitsItem* items, const uint32_t* chunk_item,
                              Partial* partials, uint32_t chunks, hipStream_t s);
+hipError_t launch_batch_scan_bound(bool slots, const BatchEntry* entries, const uint32_t* tile_entry,
+                                   const uint32_t* entry_req, const uint32_t* order, BatchBoundWords* words,
+                                   uint32_t* slices, Hit* hits, Partial* partials, uint32_t tiles, hipStream_t s);
+hipError_t launch_batch_bound(int dev, int J, int mode, const BatchBoundItem* items, const uint32_t* chunk_item,
+                              const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s);
+hipError_t launch_merge_segments_bound(const Partial* partials, const uint32_t* seg, const BatchBoundWords* words,
+                                       const Hit* hits, Hit* packed, uint64_t limit, const unsigned long long* base_in,
+                                       unsigned long long* base_out, BatchBoundResult* results, uint32_t requests,
+                                       hipStream_t s);
 hipError_t launch_merge_segments_hits(const Partial* partials, const uint32_t* seg, const BatchHitsWords* words,
                                       const Hit* hits, Hit* packed, uint64_t limit, const unsigned long long* base_in,
                                       unsigned long long* base_out, BatchHitsResult* results, uint32_t requests,
@@ -131,7 +140,21 @@ constexpr uint32_t kBatchResults = 1u << 16;   // results of the batch passes in
 // carries two words per slot (its item or entry, and the order), a GenArgs and the words per request
 // and 560-byte items, at most 8 * 2^18 + 8,192 * 136 + 4,096 * (128 + 24 + 4) + 1,024 * 560 + 8,192 * 4
 // = ~4.3 MiB, more than kBatchTableBytes
+// (the passes of mh_search_first_hits_batch use the same buffer: no GenArgs per request, 80-byte words
+// and 624-byte items, at most 8 * 2^18 + 8,192 * 140 + 4,097 * 4 + 4,096 * 80 + 1,024 * 624 = ~4.1 MiB)
 constexpr size_t kFirstBatchFastTableBytes = 5u << 20;
+// the largest pass of either kind fits: its tiles and chunks share kMaxBlocksPerLaunch slots (two
+// words each), plus every per-entry, per-request and per-item table at its limit and 16 bytes of
+// alignment for each of the nine tables
+static_assert(8u * (size_t)mh::kMaxBlocksPerLaunch + mh::kBatchMaxEntries * (sizeof(mh::BatchEntry) + 4u) +
+                      (mh::kBatchMaxRequests + 1u) * 4u +
+                      mh::kBatchMaxRequests * (sizeof(mh::GenArgs) + sizeof(mh::BatchFirstWords)) +
+                      mh::kBatchMaxFastItems * sizeof(mh::BatchFirstItem) + 9u * 16u <= kFirstBatchFastTableBytes,
+              "a first-hit pass with fast pieces fits its table buffer");
+static_assert(8u * (size_t)mh::kMaxBlocksPerLaunch + mh::kBatchMaxEntries * (sizeof(mh::BatchEntry) + 4u) +
+                      (mh::kBatchMaxRequests + 1u) * 4u + mh::kBatchMaxRequests * sizeof(mh::BatchBoundWords) +
+                      mh::kBatchMaxFastItems * sizeof(mh::BatchBoundItem) + 9u * 16u <= kFirstBatchFastTableBytes,
+              "a first-k-hits pass fits its table buffer");
 
 struct Timed {
     hipEvent_t start = nullptr, stop = nullptr;
@@ -194,6 +217,11 @@ struct DevCtx {
     mh::BatchHitsResult* h_hres = nullptr;  // pinned
     mh::Hit* d_hpacked = nullptr;   // MH_HITS_MAX_CAP entries: what the regions of a window kept, packed by the merges
     uint64_t* d_hbase = nullptr;    // two words: entries packed by the window's passes so far (written and read in turn)
+    // batched first k hits (mh_search_first_hits_batch), allocated by the first such call; the hit buffer, the packed
+    // entries and the base words are mh_search_hits_batch's, the tables' buffer mh_search_first_batch_ex's
+    mh::BatchBoundResult* d_kres = nullptr;  // one result per request of the passes in flight
+    mh::BatchBoundResult* h_kres = nullptr;  // pinned
+    uint32_t* d_bslices = nullptr;           // kFirstHitsSlices counters per request of one pass (kBatchMaxRequests of them)
 #ifdef MH_DEV_HOOKS
     uint32_t keep = 0;        // this call's coarse-hash word (MINEHIP_DEV_HASH_KEEP; 0: unset)
     bool keep_fast = false;   // ... and the fast code object in use is the variant that reads it
@@ -737,10 +765,17 @@ bool hit_by_nonce(const mh::Hit& x, const mh::Hit& y) { return x.nonce < y.nonce
 // of the buffer per window; a window that overflows the buffer all the same is halved and scanned
 // again (one of at most `slots` nonces cannot overflow), one that fits is complete, so sorted and
 // appended.  The last window's entries are all kept: *list may hold more than `want`.
+// widen (the rebuilds of mh_search_first_hits_batch only; mh_search_hits and mh_search_first_hits walk
+// as they always did): after a window that fit the next one is twice as wide again, up to the first
+// size, so that two hits that lie close together narrow the windows around them only.  A walk that
+// keeps its narrowest width takes range / smallest gap scans with a buffer of one entry, and a batch
+// under a small MINEHIP_HITS_SLOTS rebuilds most of its requests.  The widths decide which windows
+// are scanned, never what the list holds.
 int hits_window_walk(DevCtx* c, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, uint64_t slots,
-                     uint64_t want, double spacing, std::vector<mh::Hit>* list) {
+                     uint64_t want, double spacing, std::vector<mh::Hit>* list, bool widen = false) {
     const double per_window = std::max(1.0, (double)slots / 4.0 * spacing);
     uint64_t w = per_window >= 9.0e18 ? (uint64_t)9.0e18 : (uint64_t)per_window;
+    const uint64_t w0 = w;
     std::vector<mh::Hit> win;
     uint64_t cur = lower;
     list->clear();
@@ -757,6 +792,7 @@ int hits_window_walk(DevCtx* c, const mh::Prefix& pre, uint64_t lower, uint64_t 
         list->insert(list->end(), win.begin(), win.end());
         if (hi == upper) break;
         cur = hi + 1u;
+        if (widen && w < w0) w = w0 - w < w ? w0 : w * 2u;
     }
     return MH_OK;
 }
@@ -818,8 +854,9 @@ int search_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t up
 // When the device buffer dropped entries, which ones depends on timing: the list is rebuilt from
 // `lower` upward by the window walk of mh_search_hits, on the non-stopping kernels, until k entries
 // are collected or `upper` is reached.
+// widen_walk: hits_window_walk's `widen`, for the rebuilds and fallbacks of mh_search_first_hits_batch.
 int search_first_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint64_t upper, uint64_t target, mh_hit* hits,
-                           size_t k, mh_first_hits* out) {
+                           size_t k, mh_first_hits* out, bool widen_walk = false) {
     DevCtx* c;
     int rc = get_ctx(dev, &c);
     if (rc) return rc;
@@ -898,7 +935,8 @@ int search_first_hits_impl(int dev, const mh::Prefix& pre, uint64_t lower, uint6
         if (!got.empty()) MH_HIP(hipMemcpy(got.data(), c->d_hits, got.size() * sizeof(mh::Hit), hipMemcpyDeviceToHost));
         std::sort(got.begin(), got.end(), hit_by_nonce);
     } else {  // the buffer dropped entries: rebuild the list window by window, from the observed density
-        rc = hits_window_walk(c, pre, lower, upper, target, slots, k, std::max(1.0, (double)scanned) / (double)appended, &got);
+        rc = hits_window_walk(c, pre, lower, upper, target, slots, k, std::max(1.0, (double)scanned) / (double)appended, &got,
+                              widen_walk);
         if (rc) return rc;
     }
     out->stored = std::min<uint64_t>(got.size(), k);
@@ -1899,6 +1937,248 @@ int hits_batch_run_fused_ex(int dev, const mh::BatchRequest* reqs, const mh_hits
     return rc;
 }
 
+// ---- batched first k hits (mh_search_first_hits_batch) ----
+
+// The per-request checks of mh_search_first_hits_batch: batch_requests' and k; per valid request its
+// target, k and want (plan.hpp first_hits_batch_want), indexed as `valid`.
+void first_hits_batch_requests(const mh_first_hits_request* reqs, size_t n, std::vector<int>* status,
+                               std::vector<mh::BatchRequest>* valid, std::vector<uint64_t>* targets,
+                               std::vector<uint64_t>* ks, std::vector<uint64_t>* wants) {
+    status->assign(n, MH_OK);
+    valid->clear();
+    targets->clear();
+    ks->clear();
+    wants->clear();
+    for (size_t i = 0; i < n; ++i) {
+        int st = check_common(reqs[i].msg, reqs[i].len);
+        if (!st && reqs[i].k == 0) st = fail(MH_EINVAL, "k is 0");
+        if (!st && reqs[i].k > MH_HITS_MAX_CAP) st = fail(MH_EINVAL, "k is larger than MH_HITS_MAX_CAP");
+        if (!st && reqs[i].lower > reqs[i].upper) st = fail(MH_ERANGE, "lower > upper");
+        (*status)[i] = st;
+        if (st) continue;
+        valid->emplace_back();
+        mh::BatchRequest& r = valid->back();
+        mh::absorb_prefix(reqs[i].msg, reqs[i].len, &r.pre);
+        r.lower = reqs[i].lower;
+        r.upper = reqs[i].upper;
+        r.id = i;
+        targets->push_back(reqs[i].target);
+        ks->push_back(reqs[i].k);
+        wants->push_back(mh::first_hits_batch_want(reqs[i].k));
+    }
+}
+
+mh::HitsBatchLimits first_hits_batch_limits() {
+    return mh::HitsBatchLimits{kFirstBatchFastTableBytes, kBatchResults, hits_slots()};
+}
+
+int first_hits_batch_init_locked(DevCtx* c) {
+    if (!c->d_kres) MH_HIP(hipMalloc(&c->d_kres, sizeof(mh::BatchBoundResult) * kBatchResults));
+    if (!c->h_kres)
+        MH_HIP(hipHostMalloc(&c->h_kres, sizeof(mh::BatchBoundResult) * kBatchResults, hipHostMallocDefault));
+    if (!c->d_bslices)
+        MH_HIP(hipMalloc(&c->d_bslices, sizeof(uint32_t) * mh::kFirstHitsSlices * mh::kBatchMaxRequests));
+    return MH_OK;
+}
+
+// What a call hands to its passes and drains.
+struct FirstHitsBatchCall {
+    const mh::BatchRequest* reqs;
+    const mh_first_hits_request* src;
+    const uint64_t *targets, *ks, *wants;  // indexed as reqs
+    mh_hit* hits;
+    mh_first_hits_result* out;
+    std::vector<size_t>* rebuild;
+    std::vector<mh::Hit> stage;
+};
+
+// The end of a window, as hits_batch_drain: one synchronise, one copy of the entries the window's
+// regions kept, then the host's reading of every request (plan.hpp read_first_hits_batch): a request
+// whose region dropped entries goes to *rebuild; any other has its entries sorted by nonce into the
+// caller's buffer, stored = min(count, k), and with stored == k the minimum of those k, with fewer
+// the merged minimum -- nothing of it was then skipped, so scanned must be its whole range.
+int first_hits_batch_drain(DevCtx* c, FirstHitsBatchCall* call, HitsBatchPending* pend) {
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (c->prof) {
+        const int rc = harvest_locked(c);
+        if (rc) return rc;
+    }
+    uint64_t kept = 0;
+    for (size_t k = 0; k < pend->req_idx.size(); ++k) kept += std::min(c->h_kres[k].count, pend->region[k].slots);
+    if (kept > pend->st.used || kept > MH_HITS_MAX_CAP) return fail(MH_EINTERNAL, "internal: hit window larger than the buffer");
+    if (call->stage.size() < kept) call->stage.resize((size_t)kept);
+    if (kept) MH_HIP(hipMemcpy(call->stage.data(), c->d_hpacked, (size_t)kept * sizeof(mh::Hit), hipMemcpyDeviceToHost));
+    uint64_t pos = 0;  // of the request's entries in the packed order
+    for (size_t k = 0; k < pend->req_idx.size(); ++k) {
+        const size_t idx = pend->req_idx[k];
+        const mh::BatchRequest& q = call->reqs[idx];
+        const mh::HitsRegion& g = pend->region[k];
+        const mh::BatchBoundResult& res = c->h_kres[k];
+        mh_first_hits_result& r = call->out[q.id];
+        mh::Hit* first = call->stage.data() + pos;
+        pos += std::min(res.count, g.slots);
+        r.scanned = res.scanned;
+        r.path = 0;
+        uint64_t stored = 0, hash = res.hash, nonce = res.nonce;
+        if (!mh::read_first_hits_batch(first, res.count, g.slots, call->ks[idx], &stored, &hash, &nonce)) {
+            call->rebuild->push_back(idx);
+            continue;
+        }
+        if (stored < call->ks[idx] && res.scanned != q.upper - q.lower + 1u)
+            return fail(MH_EINTERNAL, "internal: fewer than k hits, but the fused scan did not hash the whole range");
+        r.stored = stored;
+        r.hash = hash;
+        r.nonce = nonce;
+        for (uint64_t i = 0; i < stored; ++i) call->hits[r.offset + i] = mh_hit{first[i].hash, first[i].nonce};
+    }
+    pend->req_idx.clear();
+    pend->region.clear();
+    pend->passes = 0;
+    return MH_OK;
+}
+
+// One pass: its image (plan.cpp build_first_hits_batch_image: every table, the requests' words with
+// their initial values, the items with the addresses of their request's words, region and counters)
+// checked and copied in one H2D copy, a memset of the pass's slice counters, then on the one stream
+// batch_scan_bound[_slots] for the generic entries, one batch_bound<J, MODE> launch per layout in the
+// plan's order, merge_segments_bound and one D2H copy of {hash, nonce, count, scanned} per request.
+// Windows, regions and drains are hits_batch_run_pass_ex's with the wants in the caps' place; the
+// profile counts the launches as that function does.
+int first_hits_batch_run_pass(DevCtx* c, FirstHitsBatchCall* call, const std::vector<mh::BatchPiece>* pieces,
+                              const mh::BatchTables& t, const mh::BatchFastTables& f, uint32_t slot_cap,
+                              const mh::HitsBatchLimits& lim, bool rank_major, HitsBatchPending* pend) {
+    for (size_t k = 0; k < f.items.size(); ++k) {
+        const mh::BatchPiece& p = (*pieces)[f.piece[k]];
+        if (f.items[k].args.mode >= mh::kModeOneEarly && !early_piece_ok(f.items[k].args, p.J))
+            return fail(MH_EINTERNAL, "internal: bad Early piece (an enumerated digit outside word J)");
+    }
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const mh::FirstHitsBatchLayout l = mh::first_hits_batch_layout(ne, nreq, tiles, f.items.size(), f.chunk_item.size());
+    if (l.bytes > kFirstBatchFastTableBytes || nreq > kBatchResults || nreq > mh::kBatchMaxRequests)
+        return fail(MH_EINTERNAL, "internal: batch pass too large");
+    // the event pool cannot take the pass's launches: a drain of its own
+    if (c->prof && c->used + 1 + (int)f.launches.size() > kEventPairs) {
+        const int rc = first_hits_batch_drain(c, call, pend);
+        if (rc) return rc;
+        mh::hits_batch_drained(&pend->st);
+    }
+    mh::FirstHitsBatchTables x;
+    mh::HitsBatchState next = pend->st;
+    const bool drain = mh::plan_first_hits_batch_pass(t, f, call->reqs, call->wants, lim, rank_major, &next, &x);
+    if (drain) {
+        const int rc = first_hits_batch_drain(c, call, pend);
+        if (rc) return rc;
+    }
+    const uint64_t used_before = drain ? 0u : pend->st.used;
+    const size_t toff = drain ? 0u : pend->st.toff;
+    pend->st = next;
+    const uint64_t window = std::min<uint64_t>(lim.window_slots, MH_HITS_MAX_CAP);
+    if (!mh::first_hits_batch_tables_ok(t, f, call->reqs, x, slot_cap, used_before, window) ||
+        toff + l.bytes > kFirstBatchFastTableBytes || pend->req_idx.size() + nreq > kBatchResults)
+        return fail(MH_EINTERNAL, "internal: bad first-hits batch tables");
+    uint8_t* h = c->h_ftab + toff;
+    uint8_t* d = c->d_ftab + toff;
+    const mh::FirstHitsBatchAddrs at{(uint64_t)(uintptr_t)d, (uint64_t)(uintptr_t)c->d_hits, (uint64_t)(uintptr_t)c->d_bslices};
+    mh::build_first_hits_batch_image(t, f, x, call->reqs, call->targets, call->ks, at, h);
+    if (!mh::first_hits_batch_image_ok(t, f, x, call->reqs, at, window, h))
+        return fail(MH_EINTERNAL, "internal: bad first-hits batch image");
+    MH_HIP(hipMemcpyAsync(d, h, l.bytes, hipMemcpyHostToDevice, c->stream));
+    MH_HIP(hipMemsetAsync(c->d_bslices, 0, nreq * sizeof(uint32_t) * mh::kFirstHitsSlices, c->stream));
+    mh::BatchBoundWords* dw = (mh::BatchBoundWords*)(d + l.o_words);
+    if (tiles) {
+        Timed* tm = nullptr;
+        if (c->prof) {  // generic class, as hits_batch_run_pass
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 1;
+            tm->var = 0;
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_scan_bound(!f.items.empty(), (const mh::BatchEntry*)d, (const uint32_t*)(d + l.o_tile),
+                                           (const uint32_t*)(d + l.o_ereq), (const uint32_t*)(d + l.o_order), dw,
+                                           c->d_bslices, c->d_hits, c->d_partials, (uint32_t)tiles, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[4] += t.nonces;
+        }
+    }
+    for (const mh::BatchFastLaunch& fl : f.launches) {
+        Timed* tm = nullptr;
+        if (c->prof) {
+            tm = &c->pool[(size_t)c->used++];
+            tm->kind = 0;
+            tm->var = var_index(fl.J, fl.mode, (int)f.items[fl.item0].args.L);
+            MH_HIP(hipEventRecord(tm->start, c->stream));
+        }
+        MH_HIP(mh::launch_batch_bound(c->dev, fl.J, fl.mode, (const mh::BatchBoundItem*)(d + l.o_item),
+                                      (const uint32_t*)(d + l.o_chunk) + fl.chunk0,
+                                      (const uint32_t*)(d + l.o_corder) + fl.chunk0, c->d_partials, fl.chunks, c->stream));
+        if (tm) {
+            MH_HIP(hipEventRecord(tm->stop, c->stream));
+            c->cnt[0] += 1;
+            c->var[tm->var].launches += 1;
+            for (uint32_t k = fl.item0; k < fl.item0 + fl.items; ++k) {
+                const mh::BatchPiece& p = (*pieces)[f.piece[k]];
+                c->cnt[1] += p.count;
+                c->cnt[3] += p.count * (uint64_t)p.ops;
+                c->cnt[6] += p.count * (uint64_t)p.nslots;
+                VarStat& v = c->var[var_index(p.J, p.mode, p.L)];
+                v.nonces += p.count;
+                v.ops += p.count * (uint64_t)p.ops;
+                v.slots += p.count * (uint64_t)p.nslots;
+            }
+        }
+    }
+    const size_t roff = pend->req_idx.size();
+    const unsigned long long* base_in = pend->passes ? (const unsigned long long*)c->d_hbase + (pend->passes & 1u) : nullptr;
+    unsigned long long* base_out = (unsigned long long*)c->d_hbase + ((pend->passes + 1u) & 1u);
+    MH_HIP(mh::launch_merge_segments_bound(c->d_partials, (const uint32_t*)(d + l.o_seg), dw, c->d_hits, c->d_hpacked,
+                                           pend->st.used, base_in, base_out, c->d_kres + roff, (uint32_t)nreq, c->stream));
+    ++pend->passes;
+    MH_HIP(hipMemcpyAsync(c->h_kres + roff, c->d_kres + roff, nreq * sizeof(mh::BatchBoundResult), hipMemcpyDeviceToHost,
+                          c->stream));
+    pend->req_idx.insert(pend->req_idx.end(), t.req_idx.begin(), t.req_idx.end());
+    pend->region.insert(pend->region.end(), x.region.begin(), x.region.end());
+    return MH_OK;
+}
+
+// The fused passes of mh_search_first_hits_batch, under the device's lock.  items: the plan of
+// flags == 0 (plan_batch); else pieces and args (plan_batch_ex).
+int first_hits_batch_run_fused(int dev, FirstHitsBatchCall* call, const std::vector<mh::BatchItem>* items,
+                               const std::vector<mh::BatchPiece>* pieces, const std::vector<mh::FastArgs>* args, int passes,
+                               uint32_t slot_cap) {
+    DevCtx* c;
+    int rc = get_ctx(dev, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = init_locked(c, dev);
+    if (rc) return rc;
+    MH_HIP(hipSetDevice(dev));
+    rc = batch_init_locked(c);
+    if (!rc) rc = hits_batch_init_locked(c);
+    if (!rc) rc = first_batch_fast_init_locked(c);
+    if (!rc) rc = first_hits_batch_init_locked(c);
+    if (rc) return rc;
+#ifdef MH_DEV_HOOKS
+    c->keep = 0;  // mh_search_first_hits_batch refused the hash hooks; nothing of an earlier search's stays
+    c->keep_fast = c->xor_on = c->xor_fast = false;
+#endif
+    const mh::HitsBatchLimits lim = first_hits_batch_limits();
+    const bool rank_major = first_batch_rank_major();
+    HitsBatchPending pend;
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    for (int p = 0; p < passes && !rc; ++p) {
+        if (items)
+            mh::build_batch_tables(call->reqs, *items, p, &t);
+        else
+            mh::build_batch_tables_ex(call->reqs, *pieces, *args, p, &t, &f);
+        rc = first_hits_batch_run_pass(c, call, pieces, t, f, slot_cap, lim, rank_major, &pend);
+    }
+    if (!rc) rc = first_hits_batch_drain(c, call, &pend);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing of this call stays in flight
+    return rc;
+}
+
 // mh_search_batch_ex(MH_BATCH_FUSE_FAST) over n >= 1 requests, the fallbacks through `fallback`.
 int search_batch_ex_impl(int dev, const mh_request* reqs, size_t n, mh_result* out, const BatchFallback& fallback) {
     std::vector<int> status;
@@ -2594,6 +2874,146 @@ int64_t mh_hits_batch_regions_ex(const mh_hits_request* reqs, size_t n, uint32_t
         for (size_t r = 0; r < t.req_idx.size(); ++r)
             regions[t.req_idx[r]] = mh_hits_region{all[t.req_idx[r]].id, 0, p, st.window, 0, x.h.region[r].offset,
                                                    x.h.region[r].slots};
+    }
+    int64_t k = 0;
+    for (const mh_hits_region& g : regions) {
+        if (k >= cap) return cap + 1;  // cap + 1 signals truncation
+        if (out) out[k] = g;
+        ++k;
+    }
+    return k;
+}
+
+int mh_search_first_hits_batch(int dev, const mh_first_hits_request* reqs, size_t n, uint32_t flags, mh_hit* hits,
+                               size_t hits_cap, mh_first_hits_result* out) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (n == 0) return MH_OK;
+    if (!reqs || !out) return fail(MH_EINVAL, "NULL array");
+#ifdef MH_DEV_HOOKS
+    // as mh_search_first_hits: the stopping hits kernels have no variants of these hooks
+    for (const char* hook : {"MINEHIP_DEV_HASH_KEEP", "MINEHIP_DEV_HASH_XOR", "MINEHIP_DEV_CODE_OBJECT"})
+        if (const char* e = getenv(hook))
+            if (*e) return fail(MH_EINVAL, std::string("mh_search_first_hits_batch does not support ") + hook);
+#endif
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> valid;
+    std::vector<uint64_t> targets, ks, wants;
+    first_hits_batch_requests(reqs, n, &status, &valid, &targets, &ks, &wants);
+    uint64_t total = 0;  // the offsets: prefix sums of k, whatever the status; a k out of range counts as 0
+    for (size_t i = 0; i < n; ++i) {
+        out[i] = mh_first_hits_result{status[i], 0, 0, 0, 0, 0, total};
+        if (reqs[i].k <= MH_HITS_MAX_CAP) total += reqs[i].k;
+        if (total > hits_cap) return fail(MH_EINVAL, "the k add up to more than hits_cap");
+    }
+    if (!hits && total > 0) return fail(MH_EINVAL, "hits is NULL with a k > 0");
+    if (valid.empty()) return MH_OK;
+    g_err.clear();
+    const uint32_t slot_cap = batch_slots();
+    std::vector<mh::BatchItem> items;
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    std::vector<size_t> fallback;  // positions in `valid`
+    int passes = 0;
+    if (flags & MH_BATCH_FUSE_FAST) {
+        mh::plan_batch_ex(valid.data(), valid.size(), plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(),
+                          &pieces, &args);
+        for (const mh::BatchPiece& p : pieces)
+            if (p.kind != 1)
+                passes = std::max(passes, p.pass + 1);
+            else
+                fallback.push_back(p.idx);
+    } else {
+        mh::plan_batch(valid.data(), valid.size(), plan_opts(), slot_cap, &items);
+        for (const mh::BatchItem& it : items)
+            if (it.kind == 0)
+                passes = std::max(passes, it.pass + 1);
+            else
+                fallback.push_back(it.idx);
+    }
+    std::vector<size_t> rebuild;  // fused requests whose region dropped entries
+    if (passes) {
+        FirstHitsBatchCall call{valid.data(), reqs, targets.data(), ks.data(), wants.data(), hits, out, &rebuild, {}};
+        const int rc = first_hits_batch_run_fused(dev, &call, (flags & MH_BATCH_FUSE_FAST) ? nullptr : &items, &pieces, &args,
+                                                  passes, slot_cap);
+        if (rc) return rc;
+    }
+    // the rebuilt requests and the fallbacks through the mh_search_first_hits path, after the fused passes
+    for (int which = 0; which < 2; ++which)
+        for (const size_t idx : which ? fallback : rebuild) {
+            const mh::BatchRequest& r = valid[idx];
+            mh_first_hits_result& o = out[r.id];
+            mh_first_hits h;
+            const int rc = search_first_hits_impl(dev, r.pre, r.lower, r.upper, targets[idx], hits + o.offset, (size_t)ks[idx], &h,
+                                                  true);
+            if (rc) return rc;
+            o.stored = h.stored;
+            o.scanned = h.scanned;
+            o.hash = h.hash;
+            o.nonce = h.nonce;
+            o.path = which ? 1 : 2;
+        }
+    return MH_OK;
+}
+
+int64_t mh_first_hits_batch_regions(const mh_first_hits_request* reqs, size_t n, uint32_t flags, mh_hits_region* out,
+                                    int64_t cap) {
+    g_err.clear();
+    if (flags & ~(uint32_t)MH_BATCH_FUSE_FAST) return fail(MH_EINVAL, "unknown flag");
+    if (n == 0) return 0;
+    if (!reqs) return fail(MH_EINVAL, "NULL array");
+    if (cap < 0) return fail(MH_EINVAL, "cap < 0");
+    std::vector<int> status;
+    std::vector<mh::BatchRequest> all;
+    std::vector<uint64_t> targets, ks, wants;
+    first_hits_batch_requests(reqs, n, &status, &all, &targets, &ks, &wants);
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])  // the first request mh_search_first_hits_batch would refuse
+            return fail(status[i], status[i] == MH_ERANGE      ? "lower > upper"
+                                   : status[i] == MH_ETOOLONG  ? "message longer than MH_MAX_MSG_LEN"
+                                   : reqs[i].k == 0            ? "k is 0"
+                                   : reqs[i].k > MH_HITS_MAX_CAP ? "k is larger than MH_HITS_MAX_CAP"
+                                                               : "msg is NULL");
+    const uint32_t slot_cap = batch_slots();
+    const bool fast = (flags & MH_BATCH_FUSE_FAST) != 0;
+    std::vector<mh::BatchItem> items;
+    std::vector<mh::BatchPiece> pieces;
+    std::vector<mh::FastArgs> args;
+    std::vector<mh_hits_region> regions(n);
+    int passes = 0;
+    if (fast) {
+        mh::plan_batch_ex(all.data(), n, plan_opts(), slot_cap, batch_fast_shared_lanes(), batch_fast_max(), &pieces, &args);
+        for (const mh::BatchPiece& p : pieces)
+            if (p.kind != 1)
+                passes = std::max(passes, p.pass + 1);
+            else
+                regions[p.idx] = mh_hits_region{p.req, 1, -1, -1, 0, 0, 0};
+    } else {
+        mh::plan_batch(all.data(), n, plan_opts(), slot_cap, &items);
+        for (const mh::BatchItem& it : items)
+            if (it.kind == 0)
+                passes = std::max(passes, it.pass + 1);
+            else
+                regions[it.idx] = mh_hits_region{it.req, 1, -1, -1, 0, 0, 0};
+    }
+    const mh::HitsBatchLimits lim = first_hits_batch_limits();
+    const bool rank_major = first_batch_rank_major();
+    mh::HitsBatchState st;
+    mh::BatchTables t;
+    mh::BatchFastTables f;
+    mh::FirstHitsBatchTables x;
+    for (int p = 0; p < passes; ++p) {
+        if (fast)
+            mh::build_batch_tables_ex(all.data(), pieces, args, p, &t, &f);
+        else
+            mh::build_batch_tables(all.data(), items, p, &t);
+        const uint64_t before = st.used;
+        const bool drain = mh::plan_first_hits_batch_pass(t, f, all.data(), wants.data(), lim, rank_major, &st, &x);
+        if (!mh::first_hits_batch_tables_ok(t, f, all.data(), x, slot_cap, drain ? 0u : before, lim.window_slots))
+            return fail(MH_EINTERNAL, "internal: bad first-hits batch tables");
+        for (size_t r = 0; r < t.req_idx.size(); ++r)
+            regions[t.req_idx[r]] = mh_hits_region{all[t.req_idx[r]].id, 0, p, st.window, 0, x.region[r].offset,
+                                                   x.region[r].slots};
     }
     int64_t k = 0;
     for (const mh_hits_region& g : regions) {

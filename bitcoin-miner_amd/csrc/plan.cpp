@@ -1,6 +1,7 @@
 // plan.cpp -- see plan.hpp.
 #include "plan.hpp"
 
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
@@ -1252,6 +1253,183 @@ bool hits_batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, con
         const uint32_t r = x.item_req[k];
         const BatchFastItem& it = f.items[k];
         if (r >= nreq || it.slot0 < t.seg[r] || (uint64_t)it.slot0 + it.args.n_chunks > t.seg[r + 1]) return false;
+    }
+    return true;
+}
+
+// ---- batched first k hits ----
+
+FirstHitsBatchLayout first_hits_batch_layout(size_t entries, size_t requests, size_t tiles, size_t items, size_t chunks) {
+    static_assert(sizeof(BatchBoundItem) % 16 == 0 && sizeof(BatchBoundWords) % 16 == 0, "tables stay 16-byte aligned");
+    FirstHitsBatchLayout l;
+    l.o_seg = align16(entries * sizeof(BatchEntry));
+    l.o_tile = l.o_seg + align16((requests + 1u) * sizeof(uint32_t));
+    l.o_ereq = l.o_tile + align16(tiles * sizeof(uint32_t));
+    l.o_order = l.o_ereq + align16(entries * sizeof(uint32_t));
+    l.o_words = l.o_order + align16(tiles * sizeof(uint32_t));
+    l.o_item = l.o_words + requests * sizeof(BatchBoundWords);
+    l.o_chunk = l.o_item + items * sizeof(BatchBoundItem);
+    l.o_corder = l.o_chunk + align16(chunks * sizeof(uint32_t));
+    l.bytes = l.o_corder + align16(chunks * sizeof(uint32_t));
+    return l;
+}
+
+bool plan_first_hits_batch_pass(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                                const uint64_t* wants, const HitsBatchLimits& lim, bool rank_major,
+                                HitsBatchState* st, FirstHitsBatchTables* out) {
+    const size_t bytes = first_hits_batch_layout(t.entries.size(), t.req_idx.size(), t.tile_entry.size(), f.items.size(),
+                                                 f.chunk_item.size()).bytes;
+    HitsBatchTables h;
+    const bool drain = plan_hits_pass(t, bytes, reqs, wants, lim, st, &h);
+    build_first_batch_tables_ex(t, f, rank_major, &out->o);
+    out->region.swap(h.region);
+    return drain;
+}
+
+bool first_hits_batch_tables_ok(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                                const FirstHitsBatchTables& x, uint32_t slot_cap, uint64_t used_before,
+                                uint64_t window_slots) {
+    if (f.items.empty()) {
+        if (!f.chunk_item.empty() || !f.launches.empty() || !batch_tables_ok(t, slot_cap)) return false;
+    } else if (!batch_tables_ex_ok(t, f, slot_cap)) {
+        return false;
+    }
+    const size_t tiles = t.tile_entry.size(), nreq = t.req_idx.size();
+    if (nreq > kBatchMaxRequests) return false;  // one set of slice counters per request of a pass
+    HitsBatchTables h;
+    h.entry_req = x.o.entry_req;
+    h.region = x.region;
+    if (!hits_batch_tables_ok(t, reqs, h, used_before, window_slots)) return false;
+    for (size_t ei = 0; ei < t.entries.size(); ++ei) {  // every entry's request owns all of the entry's slots
+        const BatchEntry& e = t.entries[ei];
+        const uint32_t r = x.o.entry_req[ei];  // < nreq (entry_requests_ok)
+        if (e.slot0 < t.seg[r] || (uint64_t)e.slot0 + batch_tiles(e.g.first, e.g.count) > t.seg[r + 1u]) return false;
+    }
+    if (x.o.item_req.size() != f.items.size()) return false;
+    for (size_t k = 0; k < f.items.size(); ++k) {  // and every item's request all of the item's
+        const uint32_t r = x.o.item_req[k];
+        const BatchFastItem& it = f.items[k];
+        if (r >= nreq || it.slot0 < t.seg[r] || (uint64_t)it.slot0 + it.args.n_chunks > t.seg[r + 1]) return false;
+    }
+    if (x.o.tile_order.size() != tiles || !is_permutation(x.o.tile_order.data(), tiles)) return false;
+    if (x.o.chunk_order.size() != f.chunk_item.size()) return false;
+    for (const BatchFastLaunch& l : f.launches)  // l.chunk0 + l.chunks <= chunk_item.size() (batch_tables_ex_ok)
+        if (!is_permutation(x.o.chunk_order.data() + l.chunk0, l.chunks)) return false;
+    return true;
+}
+
+namespace {
+// memcpy / memcmp that take an empty table (a null pointer with n == 0)
+inline void copy_table(void* dst, const void* src, size_t n) {
+    if (n) memcpy(dst, src, n);
+}
+inline bool same_table(const void* a, const void* b, size_t n) { return n == 0 || memcmp(a, b, n) == 0; }
+// the device address of field `member` of request r's words in an image at `image`
+#define MH_WORD_ADDR(image, lay, r, member) \
+    ((image) + (lay).o_words + (uint64_t)(r) * sizeof(BatchBoundWords) + offsetof(BatchBoundWords, member))
+}  // namespace
+
+void build_first_hits_batch_image(const BatchTables& t, const BatchFastTables& f, const FirstHitsBatchTables& x,
+                                  const BatchRequest* reqs, const uint64_t* targets, const uint64_t* ks,
+                                  const FirstHitsBatchAddrs& at, uint8_t* image) {
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t ni = f.items.size(), chunks = f.chunk_item.size();
+    const FirstHitsBatchLayout l = first_hits_batch_layout(ne, nreq, tiles, ni, chunks);
+    memset(image, 0, l.bytes);
+    copy_table(image, t.entries.data(), ne * sizeof(BatchEntry));
+    copy_table(image + l.o_seg, t.seg.data(), (nreq + 1u) * sizeof(uint32_t));
+    copy_table(image + l.o_tile, t.tile_entry.data(), tiles * sizeof(uint32_t));
+    copy_table(image + l.o_ereq, x.o.entry_req.data(), ne * sizeof(uint32_t));
+    copy_table(image + l.o_order, x.o.tile_order.data(), tiles * sizeof(uint32_t));
+    BatchBoundWords* w = (BatchBoundWords*)(image + l.o_words);
+    for (size_t r = 0; r < nreq; ++r) {
+        const BatchRequest& q = reqs[t.req_idx[r]];
+        const uint64_t span = q.upper - q.lower;
+        w[r] = BatchBoundWords{targets[t.req_idx[r]], 0ull, x.region[r].offset, x.region[r].slots, ks[t.req_idx[r]], ~0ull,
+                               q.lower, span, first_hits_shift(span), 0u, 0ull};
+    }
+    BatchBoundItem* items = (BatchBoundItem*)(image + l.o_item);
+    for (size_t k = 0; k < ni; ++k) {
+        const uint32_t r = x.o.item_req[k];
+        BatchBoundItem it;
+        memset(&it, 0, sizeof it);
+        it.args = f.items[k].args;
+        it.unused = nullptr;
+        it.h.h = HitsArgs{w[r].target, (unsigned long long*)MH_WORD_ADDR(at.image, l, r, cursor),
+                          (Hit*)(at.hits + w[r].offset * sizeof(Hit)), w[r].slots};
+        it.h.k = w[r].k;
+        it.h.bound = (unsigned long long*)MH_WORD_ADDR(at.image, l, r, bound);
+        it.h.slices = (uint32_t*)(at.slices + (uint64_t)r * kFirstHitsSlices * sizeof(uint32_t));
+        it.h.lower = w[r].lower;
+        it.h.span = w[r].span;
+        it.h.shift = w[r].shift;
+        it.h.pad_ = 0u;
+        it.h.scanned = (unsigned long long*)MH_WORD_ADDR(at.image, l, r, scanned);
+        it.chunk0 = f.items[k].chunk0;
+        it.slot0 = f.items[k].slot0;
+        items[k] = it;
+    }
+    copy_table(image + l.o_chunk, f.chunk_item.data(), chunks * sizeof(uint32_t));
+    copy_table(image + l.o_corder, x.o.chunk_order.data(), chunks * sizeof(uint32_t));
+}
+
+bool first_hits_batch_image_ok(const BatchTables& t, const BatchFastTables& f, const FirstHitsBatchTables& x,
+                               const BatchRequest* reqs, const FirstHitsBatchAddrs& at, uint64_t window_slots,
+                               const uint8_t* image) {
+    const size_t ne = t.entries.size(), nreq = t.req_idx.size(), tiles = t.tile_entry.size();
+    const size_t ni = f.items.size(), chunks = f.chunk_item.size();
+    if (nreq > kBatchMaxRequests || x.region.size() != nreq || x.o.item_req.size() != ni) return false;
+    if (x.o.entry_req.size() != ne || x.o.tile_order.size() != tiles || x.o.chunk_order.size() != chunks) return false;
+    const FirstHitsBatchLayout l = first_hits_batch_layout(ne, nreq, tiles, ni, chunks);
+    if (!same_table(image + l.o_ereq, x.o.entry_req.data(), ne * sizeof(uint32_t)) ||
+        !same_table(image + l.o_order, x.o.tile_order.data(), tiles * sizeof(uint32_t)) ||
+        !same_table(image + l.o_chunk, f.chunk_item.data(), chunks * sizeof(uint32_t)) ||
+        !same_table(image + l.o_corder, x.o.chunk_order.data(), chunks * sizeof(uint32_t)))
+        return false;
+    const BatchBoundWords* w = (const BatchBoundWords*)(image + l.o_words);
+    for (size_t r = 0; r < nreq; ++r) {
+        const BatchRequest& q = reqs[t.req_idx[r]];
+        const uint64_t span = q.upper - q.lower;
+        if (w[r].offset != x.region[r].offset || w[r].slots != x.region[r].slots) return false;
+        if (w[r].offset > window_slots || w[r].slots > window_slots - w[r].offset) return false;
+        if (w[r].lower != q.lower || w[r].span != span || w[r].shift != first_hits_shift(span) || w[r].pad_ != 0u) return false;
+        if (first_hits_slices(span, w[r].shift) > kFirstHitsSlices) return false;
+        if (w[r].k == 0u || w[r].cursor != 0ull || w[r].bound != ~0ull || w[r].scanned != 0ull) return false;
+    }
+    const BatchBoundItem* items = (const BatchBoundItem*)(image + l.o_item);
+    for (size_t k = 0; k < ni; ++k) {
+        const uint32_t r = x.o.item_req[k];
+        if (r >= nreq) return false;
+        const BatchBoundItem& it = items[k];
+        if (memcmp(&it.args, &f.items[k].args, sizeof(FastArgs)) || it.unused != nullptr) return false;
+        if (it.chunk0 != f.items[k].chunk0 || it.slot0 != f.items[k].slot0) return false;
+        if (it.h.h.target != w[r].target || it.h.k != w[r].k || it.h.lower != w[r].lower || it.h.span != w[r].span ||
+            it.h.shift != w[r].shift || it.h.pad_ != 0u)
+            return false;
+        if ((uint64_t)it.h.h.cursor != MH_WORD_ADDR(at.image, l, r, cursor) ||
+            (uint64_t)it.h.bound != MH_WORD_ADDR(at.image, l, r, bound) ||
+            (uint64_t)it.h.scanned != MH_WORD_ADDR(at.image, l, r, scanned))
+            return false;
+        if ((uint64_t)it.h.h.hits != at.hits + w[r].offset * sizeof(Hit) || it.h.h.cap != w[r].slots) return false;
+        if ((uint64_t)it.h.slices != at.slices + (uint64_t)r * kFirstHitsSlices * sizeof(uint32_t)) return false;
+    }
+    return true;
+}
+#undef MH_WORD_ADDR
+
+bool read_first_hits_batch(Hit* got, uint64_t count, uint64_t slots, uint64_t k, uint64_t* stored, uint64_t* hash,
+                           uint64_t* nonce) {
+    if (count > slots) return false;
+    std::sort(got, got + count, [](const Hit& x, const Hit& y) { return x.nonce < y.nonce; });
+    *stored = std::min(count, k);
+    if (*stored == k && k != 0u) {
+        *hash = got[0].hash;
+        *nonce = got[0].nonce;
+        for (uint64_t i = 1; i < k; ++i)
+            if (got[i].hash < *hash || (got[i].hash == *hash && got[i].nonce < *nonce)) {
+                *hash = got[i].hash;
+                *nonce = got[i].nonce;
+            }
     }
     return true;
 }

@@ -379,4 +379,67 @@ bool hits_batch_tables_ex_ok(const BatchTables& t, const BatchFastTables& f, con
                              const HitsBatchFastTables& x, uint32_t slot_cap, uint64_t used_before,
                              uint64_t window_slots);
 
+// ---- batched first k hits (mh_search_first_hits_batch / mh_first_hits_batch_regions) ----
+// The plan is plan_batch's or plan_batch_ex's and the tables build_batch_tables[_ex]'s (targets and
+// k play no part in either; a pass without fast pieces has an empty BatchFastTables).  Windows,
+// regions and drains are plan_hits_batch_pass's with a want per request in the cap's place: a
+// request of k wants min(its nonce count, first_hits_batch_want(k)) entries of the device hit
+// buffer -- room for the hits appended before the bound takes effect -- and gets what the window has
+// left of that.  Neither constant affects a returned entry: a request that appends more than its
+// region holds is rebuilt by the caller.
+constexpr uint64_t kFirstHitsBatchFactor = 4, kFirstHitsBatchFloor = 256;
+constexpr uint64_t first_hits_batch_want(uint64_t k) {
+    return k * kFirstHitsBatchFactor > kFirstHitsBatchFloor ? k * kFirstHitsBatchFactor : kFirstHitsBatchFloor;
+}
+struct FirstHitsBatchTables {
+    FirstBatchFastTables o;          // per entry and per item its request; the tile and chunk orders
+    std::vector<HitsRegion> region;  // per request of the pass
+};
+// Where the tables of one pass lie in its image, each aligned to 16 bytes: entries, segments,
+// per-tile entry, per-entry request, tile order, per-request words (BatchBoundWords), items
+// (BatchBoundItem), per-chunk item, chunk order.
+struct FirstHitsBatchLayout {
+    size_t o_seg, o_tile, o_ereq, o_order, o_words, o_item, o_chunk, o_corder, bytes;
+};
+FirstHitsBatchLayout first_hits_batch_layout(size_t entries, size_t requests, size_t tiles, size_t items, size_t chunks);
+// plan_hits_batch_pass_ex with those bytes and the wants (wants[BatchPiece::idx], as caps there),
+// plus the order tables of the first-hit batch (build_first_batch_tables_ex).
+bool plan_first_hits_batch_pass(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                                const uint64_t* wants, const HitsBatchLimits& lim, bool rank_major,
+                                HitsBatchState* st, FirstHitsBatchTables* out);
+// Checked before every pass: batch_tables_ok (no fast piece) or batch_tables_ex_ok, the regions as
+// hits_batch_tables_ok checks them, every entry's and item's request the one whose segment holds all
+// of its slots, the orders permutations (first_batch_tables_ex_ok's conditions), and no more
+// requests than a pass's slice counters serve (kBatchMaxRequests).
+bool first_hits_batch_tables_ok(const BatchTables& t, const BatchFastTables& f, const BatchRequest* reqs,
+                                const FirstHitsBatchTables& x, uint32_t slot_cap, uint64_t used_before,
+                                uint64_t window_slots);
+// The device addresses an image is built for: where the image itself goes, the device hit buffer
+// and the pass's slice counters (kFirstHitsSlices per request of a pass).
+struct FirstHitsBatchAddrs {
+    uint64_t image, hits, slices;
+};
+// Write the pass's image (first_hits_batch_layout(...).bytes bytes at `image`): the tables, the
+// requests' words with their initial values (cursor 0, bound all ones, scanned 0; the slicing of
+// the request's own range) and the items, each with the device addresses of its request's words,
+// region and counters.  targets and ks are indexed as wants (BatchPiece::idx).
+void build_first_hits_batch_image(const BatchTables& t, const BatchFastTables& f, const FirstHitsBatchTables& x,
+                                  const BatchRequest* reqs, const uint64_t* targets, const uint64_t* ks,
+                                  const FirstHitsBatchAddrs& at, uint8_t* image);
+// Checked on the image before it is copied: every request's words hold its region, its own range's
+// slicing, 1 <= k and the initial values; every item's target, k, range and slicing are its
+// request's words', its cursor, bound and scanned pointers the addresses of those words, its region
+// its request's and inside the hit buffer's window, its counters its request's kFirstHitsSlices --
+// so the counters of different requests never overlap -- and the order tables are the checked ones.
+bool first_hits_batch_image_ok(const BatchTables& t, const BatchFastTables& f, const FirstHitsBatchTables& x,
+                               const BatchRequest* reqs, const FirstHitsBatchAddrs& at, uint64_t window_slots,
+                               const uint8_t* image);
+// The host's reading of one fused request after a drain: `got` holds the min(count, slots) entries
+// its region kept.  count > slots: false (which entries were kept depends on timing; the caller
+// rebuilds the request).  Otherwise the entries are sorted by nonce, *stored = min(count, k), and
+// with stored == k {*hash, *nonce} is the minimum of the first k; with stored < k it is left to the
+// caller (the merged minimum; scanned must then be the whole range).
+bool read_first_hits_batch(Hit* got, uint64_t count, uint64_t slots, uint64_t k, uint64_t* stored, uint64_t* hash,
+                           uint64_t* nonce);
+
 }  // namespace mh

@@ -70,6 +70,15 @@
 //   batch_scan_hits_slots  batch_scan_hits writing partials[slot0 + tile - tile0], as
 //                         batch_scan_slots relates to batch_scan.  merge_segments_hits serves such
 //                         passes unchanged: it reads the segments and the words, not the entries.
+//   batch_scan_bound      batch_scan_hits for mh_search_first_hits_batch: tiles in batch_scan_first's
+//                         order, skipped above their request's bound; the hits count in the request's
+//                         slices and the wave that reaches k publishes the bound.
+//   batch_scan_bound_slots  batch_scan_bound writing partials[slot0 + tile - tile0].
+//   batch_bound<J, MODE>  (fast_search.hip, -DMH_BATCH -DMH_HITS -DMH_STOP) batch_first's table, order and
+//                         grid around hits_stop's chunk body, through the request's words; a tenth
+//                         embedded code object, loaded by the first mh_search_first_hits_batch that
+//                         fuses a fast piece.
+//   merge_segments_bound  merge_segments_hits, and the request's {hash, nonce, count, scanned} out.
 //
 // Every candidate comparison is the lexicographic (hash, nonce) order, which
 // equals the reference loop's strict-< first minimum.
@@ -106,6 +115,8 @@ extern "C" const unsigned char mh_batch_first_stop_co_begin[];
 extern "C" const unsigned char mh_batch_hits_co_begin[];
 // the same source built with -DMH_HITS -DMH_STOP: hits_stop<J, MODE>, the fast kernels of mh_search_first_hits
 extern "C" const unsigned char mh_hits_stop_co_begin[];
+// the same source built with -DMH_BATCH -DMH_HITS -DMH_STOP: batch_bound<J, MODE>, the fused fast pieces of mh_search_first_hits_batch
+extern "C" const unsigned char mh_batch_bound_co_begin[];
 
 namespace mh {
 #ifdef MH_DEV_HOOKS
@@ -380,11 +391,20 @@ namespace dev {
 // HITS (batch_scan_hits): the product's own (hash, nonce) fold, and on a rare branch every nonce
 // with hash <= target takes one slot from its request's cursor and stores {hash, nonce} at
 // region[slot] if slot < region_slots (layout.hpp BatchHitsWords); no test hooks there either
-// (mh_search_hits_batch refuses them).  Without HITS the three last parameters are unused.
-template <bool FIRST, bool HITS = false>
+// (mh_search_hits_batch refuses them).  Without HITS the three parameters after bn are unused.
+// BOUND (batch_scan_bound): the product's fold with generic_scan_hits_stop's append, which whole
+// waves make: every lane of the wave calls this and runs all ten digits, so the wave stays
+// converged, and a digit outside jlo .. jhi, or any digit of a lane that is not `live` (it has no
+// decade of the tile; u is then any decade of the entry), is hashed and ignored.  Per step, the
+// wave's hits first count in their slices of the request's range, the counts are back before the
+// lead lane advances the request's cursor, the hits go to the request's region below its end, and
+// the wave whose cursor value plus its own hits reaches k publishes the request's bound (hs: the
+// request's words as a HitsStopArgs).  No test hooks.  Without BOUND the two last parameters are unused.
+template <bool FIRST, bool HITS = false, bool BOUND = false>
 __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32_t jlo, uint32_t jhi, uint64_t target,
                                             uint64_t& bh, uint64_t& bn, unsigned long long* cursor = nullptr,
-                                            Hit* region = nullptr, uint64_t region_slots = 0) {
+                                            Hit* region = nullptr, uint64_t region_slots = 0,
+                                            const HitsStopArgs* hs = nullptr, bool live = true) {
     // digits of u; u <= (2^64 - 1) / 10 has at most 19
     constexpr uint64_t P10[19] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
                                   100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull,
@@ -441,7 +461,7 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
     const uint32_t w16 = w[16];
     const uint64_t n0 = u * 10u;
 #pragma unroll 1
-    for (uint32_t j = jlo; j <= jhi; ++j) {
+    for (uint32_t j = BOUND ? 0u : jlo; j <= (BOUND ? 9u : jhi); ++j) {
         const uint32_t dj = j << lsh;
         uint32_t x[16];
 #pragma unroll
@@ -477,6 +497,27 @@ __device__ __forceinline__ void scan_decade(const GenArgs& a, uint64_t u, uint32
                 const unsigned long long slot = atomicAdd(cursor, 1ull);
                 if (slot < region_slots) region[slot] = Hit{hash, n};
             }
+        }
+        if constexpr (BOUND) {
+            const bool mine = live && j >= jlo && j <= jhi;
+            const bool hit = mine && hash <= target;
+            const uint64_t hm = __builtin_amdgcn_ballot_w64(hit);
+            if (hm) {  // one value per wave: generic_scan_hits_stop's append
+                const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                const uint32_t lead = (uint32_t)__builtin_ctzll(hm);
+                uint32_t back = 0u;
+                if (hit) back = atomicAdd(first_hits_slice(*hs, n), 1u);
+                asm volatile("" ::"v"(back) : "memory");  // the slice counts are back before the cursor advances
+                unsigned long long taken = 0ull;
+                if (lane == lead) taken = atomicAdd(hs->h.cursor, (unsigned long long)__builtin_popcountll(hm));
+                const uint64_t first =
+                    ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(taken >> 32), (int)lead) << 32) |
+                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)taken, (int)lead);
+                const uint64_t slot = first + (uint32_t)__builtin_popcountll(hm & ((1ull << lane) - 1ull));
+                if (hit && slot < hs->h.cap) hs->h.hits[slot] = Hit{hash, n};
+                if (first + (uint32_t)__builtin_popcountll(hm) >= hs->k) publish_first_hits_bound(*hs, lane);
+            }
+            if (!mine) continue;
         }
         if (lex_less(hash, n, bh, bn)) {
             bh = hash;
@@ -684,6 +725,104 @@ __global__ __launch_bounds__(kBlockThreads) void batch_scan_hits_slots(const Bat
     batch_scan_hits_tile<true>(entries, tile_entry, entry_req, words, hits, partials);
 }
 
+// batch_scan for mh_search_first_hits_batch: batch_scan_hits' tile -- the product's
+// (hash, nonce) minimum, every hit appended through the request's cursor into the request's region
+// of the device hit buffer, nothing stored at or past the region's end -- taken in
+// batch_scan_first's order: workgroup b runs tile order[b], the host's rank-major dispatch order, a
+// permutation of the pass's tiles.  The tile's request (entry_req[entry]) has its device words
+// (layout.hpp BatchBoundWords) and kFirstHitsSlices slice counters at slices + request *
+// kFirstHitsSlices.  Before any hashing thread 0 reads the request's bound once; a tile whose
+// smallest in-range nonce is above it writes the sentinel and ends (at least k hits of the request
+// are <= the word's value, so none of the tile's nonces is among the request's k smallest hits; the
+// word only decreases, so a stale read only skips less).  A tile that runs adds its valid nonces to
+// the request's `scanned`; its hits count in their slices before the cursor advances, and the wave
+// whose cursor value plus its own hits reaches k publishes the bound (scan_decade<.., BOUND>).  No
+// stop inside a tile, no workgroup waits for another: the grid always drains.  No test hooks.
+// SLOTS: the tile writes partials[slot0 + tile - tile0] instead of partials[tile] (batch_scan_bound_slots).
+template <bool SLOTS>
+__device__ __forceinline__ void batch_scan_bound_tile(const BatchEntry* __restrict__ entries,
+                                                      const uint32_t* __restrict__ tile_entry,
+                                                      const uint32_t* __restrict__ entry_req,
+                                                      const uint32_t* __restrict__ order, BatchBoundWords* words,
+                                                      uint32_t* slices, Hit* hits, Partial* __restrict__ partials) {
+    using namespace dev;
+    __shared__ uint32_t s_skip;
+    const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[blockIdx.x]);
+    const uint32_t ei = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_entry[tile]);
+    const uint32_t ri = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry_req[ei]);
+    const BatchEntry& e = entries[ei];
+    const GenArgs& a = e.g;
+    BatchBoundWords* w = words + ri;
+    const uint32_t slot = SLOTS ? e.slot0 + (tile - e.tile0) : tile;
+    const uint64_t first = a.first, lastn = a.first + (a.count - 1u);
+    const uint64_t u_first = first / 10u, u_last = lastn / 10u;
+    const uint32_t j_first = (uint32_t)(first - u_first * 10u), j_last = (uint32_t)(lastn - u_last * 10u);
+    const uint64_t nd = u_last - u_first + 1u;
+    const uint64_t base = (uint64_t)(tile - e.tile0) * kBatchTileDecades;  // < nd (the host's table check)
+    // the tile's nonces n_lo .. n_hi, ragged at the entry's two ends (batch_scan_first's)
+    const uint64_t d_lo = u_first + base;
+    const uint64_t d_hi = nd - base > (uint64_t)kBatchTileDecades ? d_lo + (kBatchTileDecades - 1u) : u_last;
+    const uint64_t n_lo = base == 0u ? first : d_lo * 10u;  // the tile's smallest in-range nonce
+    const uint64_t n_hi = d_hi == u_last ? lastn : d_hi * 10u + 9u;
+    if (threadIdx.x == 0)
+        s_skip = n_lo > __hip_atomic_load(&w->bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
+    __syncthreads();
+    if (s_skip) {  // one value per workgroup
+        if (threadIdx.x == 0) partials[slot] = Partial{~0ull, ~0ull};
+        return;
+    }
+    // the request's words as the stopping hits kernels take them; none but cursor, bound and scanned
+    // (and the counters) is written on the device
+    const HitsStopArgs hs{HitsArgs{w->target, &w->cursor, hits + w->offset, w->slots},
+                          w->k,
+                          &w->bound,
+                          slices + (size_t)ri * kFirstHitsSlices,
+                          w->lower,
+                          w->span,
+                          w->shift,
+                          0u,
+                          &w->scanned};
+    uint64_t bh = ~0ull, bn = ~0ull;
+#pragma unroll 1
+    for (int k = 0; k < kBatchDecades; ++k) {
+        // every lane runs a decade, so that the waves stay whole for the append: one past the
+        // entry's last runs the entry's first with nothing of it counted
+        const uint64_t off = base + (uint32_t)k * (uint32_t)kBlockThreads + threadIdx.x;
+        const bool live = off < nd;
+        const uint64_t u = live ? u_first + off : u_first;
+        scan_decade<false, false, true>(a, u, live && off == 0u ? j_first : 0u, u == u_last ? j_last : 9u, hs.h.target, bh,
+                                        bn, nullptr, nullptr, 0, &hs, live);
+    }
+    block_min(bh, bn);
+    if (threadIdx.x == 0) {
+        partials[slot] = Partial{bh, bn};
+        atomicAdd(&w->scanned, (unsigned long long)(n_hi - n_lo + 1u));
+    }
+}
+
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_bound(const BatchEntry* __restrict__ entries,
+                                                                  const uint32_t* __restrict__ tile_entry,
+                                                                  const uint32_t* __restrict__ entry_req,
+                                                                  const uint32_t* __restrict__ order,
+                                                                  BatchBoundWords* words, uint32_t* slices, Hit* hits,
+                                                                  Partial* __restrict__ partials) {
+    batch_scan_bound_tile<false>(entries, tile_entry, entry_req, order, words, slices, hits, partials);
+}
+
+// batch_scan_bound for a pass of mh_search_first_hits_batch(MH_BATCH_FUSE_FAST) that holds fast
+// pieces: a request's slot segment holds its tiles and its fast chunks in nonce order, so an entry's
+// slots start at slot0, apart from tile0; order is still a permutation of the pass's tiles.  The
+// words, the region and the counters a tile uses are the ones batch_bound's chunks of the same
+// request use.
+__global__ __launch_bounds__(kBlockThreads) void batch_scan_bound_slots(const BatchEntry* __restrict__ entries,
+                                                                        const uint32_t* __restrict__ tile_entry,
+                                                                        const uint32_t* __restrict__ entry_req,
+                                                                        const uint32_t* __restrict__ order,
+                                                                        BatchBoundWords* words, uint32_t* slices,
+                                                                        Hit* hits, Partial* __restrict__ partials) {
+    batch_scan_bound_tile<true>(entries, tile_entry, entry_req, order, words, slices, hits, partials);
+}
+
 // One workgroup per request of the pass: results[r] = the lexicographic minimum of
 // partials[seg[r] .. seg[r + 1]) (never empty; the host checks the table before the launch).
 __global__ __launch_bounds__(kBlockThreads) void merge_segments(const Partial* __restrict__ partials,
@@ -818,6 +957,52 @@ __global__ __launch_bounds__(kBlockThreads) void merge_segments_hits(const Parti
     if (threadIdx.x == 0) results[r] = BatchHitsResult{h, n, count};
 }
 
+// merge_segments_hits for mh_search_first_hits_batch: the same fold and the same packing of the
+// entries the request's region kept, over BatchBoundWords, and results[r] = {hash, nonce, the
+// request's cursor, its scanned count}, all final since every tile and chunk of the pass has run
+// (stream order).  The minimum is the request's only when nothing of it was skipped or left (the
+// sentinel of a skipped tile or chunk is all ones); the host uses it only then.
+__global__ __launch_bounds__(kBlockThreads) void merge_segments_bound(const Partial* __restrict__ partials,
+                                                                      const uint32_t* __restrict__ seg,
+                                                                      const BatchBoundWords* __restrict__ words,
+                                                                      const Hit* __restrict__ hits,
+                                                                      Hit* __restrict__ packed, uint64_t limit,
+                                                                      const unsigned long long* base_in,
+                                                                      unsigned long long* base_out,
+                                                                      BatchBoundResult* __restrict__ results) {
+    using namespace dev;
+    __shared__ unsigned long long s_before;
+    const uint32_t r = blockIdx.x;
+    if (threadIdx.x == 0) s_before = base_in ? *base_in : 0ull;
+    __syncthreads();
+    unsigned long long before = 0ull;
+    for (uint32_t j = threadIdx.x; j < r; j += kBlockThreads) {
+        const unsigned long long c = words[j].cursor, sl = words[j].slots;
+        before += c < sl ? c : sl;
+    }
+    if (before) atomicAdd(&s_before, before);
+    __syncthreads();
+    const uint64_t base = s_before;
+    const uint64_t count = words[r].cursor;
+    const uint64_t kept = count < words[r].slots ? count : words[r].slots;
+    const Hit* region = hits + words[r].offset;
+    for (uint64_t i = threadIdx.x; i < kept; i += kBlockThreads)
+        if (base + i < limit) packed[base + i] = region[i];
+    if (threadIdx.x == 0 && r + 1u == gridDim.x) *base_out = base + kept;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r]);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg[r + 1]);
+    uint64_t h = ~0ull, n = ~0ull;
+    for (uint32_t i = a + threadIdx.x; i < b; i += kBlockThreads) {
+        const Partial x = partials[i];
+        if (lex_less(x.hash, x.nonce, h, n)) {
+            h = x.hash;
+            n = x.nonce;
+        }
+    }
+    block_min(h, n);
+    if (threadIdx.x == 0) results[r] = BatchBoundResult{h, n, count, words[r].scanned};
+}
+
 // ---------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------
@@ -857,8 +1042,10 @@ std::map<int, uint64_t> g_xor_lib;                // the value this library's ow
 // batch_first's parameters, its marker mh_fast_batch_stop_items at sizeof(BatchFirstItem)
 // or kFastHitsStop, hits_stop<J, MODE> of the ninth (":hits_stop"; no hook replaces it): hits_scan's
 // first two parameters, a HitsStopArgs as the third, and fast_search's marker
+// or kFastBatchBound, batch_bound<J, MODE> of the tenth (":batch_bound"; no hook replaces it):
+// batch_first's parameters over BatchBoundItems, its marker mh_fast_batch_bound_items at sizeof(BatchBoundItem)
 enum FastVariant { kFastProduct = 0, kFastFirst = 1, kFastHits = 2, kFastBatch = 3, kFastBatchFirst = 4, kFastBatchHits = 5,
-                   kFastFirstStop = 6, kFastBatchStop = 7, kFastHitsStop = 8 };
+                   kFastFirstStop = 6, kFastBatchStop = 7, kFastHitsStop = 8, kFastBatchBound = 9 };
 #ifdef MH_DEV_HOOKS
 std::string batch_module_path() {
     const char* co = getenv("MINEHIP_DEV_BATCH_CODE_OBJECT");
@@ -871,14 +1058,14 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                          FastVariant variant = kFastProduct) {
     const bool first = variant == kFastFirst, hits = variant == kFastHits, batch = variant == kFastBatch;
     const bool bfirst = variant == kFastBatchFirst, bhits = variant == kFastBatchHits, fstop = variant == kFastFirstStop;
-    const bool bstop = variant == kFastBatchStop, hstop = variant == kFastHitsStop;
+    const bool bstop = variant == kFastBatchStop, hstop = variant == kFastHitsStop, bbound = variant == kFastBatchBound;
 #ifdef MH_DEV_HOOKS
     const char* co = getenv("MINEHIP_DEV_CODE_OBJECT");
     const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : hstop ? ":hits_stop" : batch ? batch_module_path()
-                             : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : (co && *co) ? co : "";
+                             : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : bbound ? ":batch_bound" : (co && *co) ? co : "";
 #else
     const std::string path = first ? ":first" : fstop ? ":first_stop" : hits ? ":hits" : hstop ? ":hits_stop" : batch ? batch_module_path()
-                             : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : "";
+                             : bfirst ? ":batch_first" : bstop ? ":batch_first_stop" : bhits ? ":batch_hits" : bbound ? ":batch_bound" : "";
 #endif
     std::lock_guard<std::mutex> g(g_mod_mu);
     auto it = g_mods.find({path, dev});
@@ -892,6 +1079,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                              : bfirst       ? hipModuleLoadData(&m, mh_batch_first_co_begin)
                              : bstop        ? hipModuleLoadData(&m, mh_batch_first_stop_co_begin)
                              : bhits        ? hipModuleLoadData(&m, mh_batch_hits_co_begin)
+                             : bbound       ? hipModuleLoadData(&m, mh_batch_bound_co_begin)
                              : path.empty() ? hipModuleLoadData(&m, mh_fast_co_begin)
                                             : hipModuleLoad(&m, path.c_str());
         if (e != hipSuccess) {
@@ -910,6 +1098,8 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                                         gsz == sizeof(BatchFirstItem)
                             : bhits ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_hits_items") == hipSuccess &&
                                         gsz == sizeof(BatchHitsItem)
+                            : bbound ? hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_batch_bound_items") == hipSuccess &&
+                                        gsz == sizeof(BatchBoundItem)
                                   : hipModuleGetGlobal(&gp, &gsz, m, "mh_fast_queue_args") == hipSuccess &&
                                         gsz == sizeof(FastArgs);
         (void)hipGetLastError();
@@ -934,6 +1124,7 @@ hipError_t fast_function(int dev, int J, int mode, hipFunction_t* f, bool* queue
                  bfirst ? "_ZN2mh11batch_firstILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
                  : bstop ? "_ZN2mh10batch_stopILi%dELi%dEEEvPKNS_14BatchFirstItemEPKjS5_PNS_7PartialE"
                  : bhits ? "_ZN2mh10batch_hitsILi%dELi%dEEEvPKNS_13BatchHitsItemEPKjPNS_7PartialE"
+                 : bbound ? "_ZN2mh11batch_boundILi%dELi%dEEEvPKNS_14BatchBoundItemEPKjS5_PNS_7PartialE"
                  : first ? "_ZN2mh10first_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : fstop ? "_ZN2mh9stop_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_9FirstArgsE"
                  : hits ? "_ZN2mh9hits_scanILi%dELi%dEEEvNS_8FastArgsEPNS_7PartialENS_8HitsArgsE"
@@ -1232,6 +1423,22 @@ hipError_t launch_batch_hits(int dev, int J, int mode, const BatchHitsItem* item
     return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
 }
 
+// launch_batch_first with batch_bound<J, mode> of the first-k-hits batch code object (loaded on dev,
+// the current device, by the first call) over BatchBoundItems: the same per-chunk table, order and
+// grid (the caller has checked the tables, the regions and the items' words, minehip.cpp
+// first_hits_batch_run_pass).  A code object without its marker at sizeof(BatchBoundItem) is refused.
+hipError_t launch_batch_bound(int dev, int J, int mode, const BatchBoundItem* items, const uint32_t* chunk_item,
+                              const uint32_t* order, Partial* partials, uint32_t chunks, hipStream_t s) {
+    if (!fast_variant_exists(J, mode) || chunks == 0 || chunks > kMaxBlocksPerLaunch) return hipErrorInvalidValue;
+    hipFunction_t fn;
+    bool marked = false;
+    const hipError_t e = fast_function(dev, J, mode, &fn, &marked, kFastBatchBound);
+    if (e != hipSuccess) return e;
+    if (!marked) return hipErrorInvalidImage;
+    void* params[] = {&items, &chunk_item, &order, &partials};
+    return hipModuleLaunchKernel(fn, chunks, 1, 1, kBlockThreads, 1, 1, 0, s, params, nullptr);
+}
+
 #ifdef MH_DEV_HOOKS
 // The hooks of the batch code object in use on dev (the current device; loaded if need be): whether
 // its kernels mask hashes by FastArgs::pad_ (*keep_ok), and x made its hash-XOR constant if it has
@@ -1325,6 +1532,30 @@ hipError_t launch_merge_segments_hits(const Partial* partials, const uint32_t* s
                                       unsigned long long* base_out, BatchHitsResult* results, uint32_t requests,
                                       hipStream_t s) {
     hipLaunchKernelGGL(merge_segments_hits, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, words, hits, packed,
+                       limit, base_in, base_out, results);
+    return hipGetLastError();
+}
+
+// One pass of a first-k-hits batch: tiles workgroups of batch_scan_bound (slots: batch_scan_bound_slots,
+// a pass that also holds fast pieces), then requests workgroups of merge_segments_bound (the caller
+// has checked the tables, the order, the regions and the slices, minehip.cpp first_hits_batch_run_pass).
+hipError_t launch_batch_scan_bound(bool slots, const BatchEntry* entries, const uint32_t* tile_entry,
+                                   const uint32_t* entry_req, const uint32_t* order, BatchBoundWords* words,
+                                   uint32_t* slices, Hit* hits, Partial* partials, uint32_t tiles, hipStream_t s) {
+    if (slots)
+        hipLaunchKernelGGL(batch_scan_bound_slots, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req,
+                           order, words, slices, hits, partials);
+    else
+        hipLaunchKernelGGL(batch_scan_bound, dim3(tiles), dim3(kBlockThreads), 0, s, entries, tile_entry, entry_req, order,
+                           words, slices, hits, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_segments_bound(const Partial* partials, const uint32_t* seg, const BatchBoundWords* words,
+                                       const Hit* hits, Hit* packed, uint64_t limit, const unsigned long long* base_in,
+                                       unsigned long long* base_out, BatchBoundResult* results, uint32_t requests,
+                                       hipStream_t s) {
+    hipLaunchKernelGGL(merge_segments_bound, dim3(requests), dim3(kBlockThreads), 0, s, partials, seg, words, hits, packed,
                        limit, base_in, base_out, results);
     return hipGetLastError();
 }

@@ -21,6 +21,9 @@ tests read like the reference (line numbers into the reference repo):
   search_hits_batch(requests, cap=4096)
                              every hit of many small requests in one GPU pass
                              (fuse_fast=True: the fast pieces of larger ones too)
+  search_first_hits_batch(requests)
+                             the k smallest hits of many requests in one GPU pass
+                             (fuse_fast=True: the fast pieces of larger ones too)
   miner_handle_batch(...)    miner_handle for the payloads a miner holds at once (fuse_fast=True:
                              the fast pieces of the larger Requests fuse too)
   Scheduler / Server         the server's chunk scheduler and message loop (depth=: how many
@@ -43,6 +46,7 @@ from ._lib import mh_batch_piece, MH_BATCH_FUSE_FAST, MH_BATCH_FAST_MAX_NONCES  
 from ._lib import mh_first_request, mh_first_result, MH_FIRST_STOP_RUNNING  # noqa: F401
 from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP, mh_first_hits  # noqa: F401
 from ._lib import mh_hits_request, mh_hits_result, mh_hits_region  # noqa: F401
+from ._lib import mh_first_hits_request, mh_first_hits_result  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -357,6 +361,78 @@ def hits_batch_regions(requests, cap=4096, fuse_fast=False, flags=None):
                                          len(requests))
     else:
         k = lib.mh_hits_batch_regions(arr, len(requests), buf, len(requests))
+    if k < 0:
+        _check(k)
+    return [{f: getattr(buf[i], f) for f, _ in mh_hits_region._fields_ if f != "reserved"} for i in range(k)]
+
+
+def _first_hits_requests(requests):
+    """(msg, lower, upper, target, k) tuples -> (mh_first_hits_request array, the message bytes it
+    points into, the offsets of the requests' entries, their sum)."""
+    keep, offsets, total = [], [], 0
+    arr = (mh_first_hits_request * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        try:
+            msg, lower, upper, target, k = r
+        except (TypeError, ValueError):
+            raise ValueError(f"request {i}: expected (msg, lower, upper, target, k), got {r!r}") from None
+        for name, v in (("lower", lower), ("upper", upper), ("target", target), ("k", k)):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= U64_MAX:
+                raise ValueError(f"request {i}: {name} = {v!r} is not a uint64")
+        m = _b(msg)
+        keep.append(m)
+        arr[i].msg, arr[i].len, arr[i].lower, arr[i].upper, arr[i].target, arr[i].k = m, len(m), lower, upper, target, k
+        offsets.append(total)
+        total += k if k <= MH_HITS_MAX_CAP else 0       # as the library counts them
+    return arr, keep, offsets, total
+
+
+def search_first_hits_batch(requests, dev=0, errors="raise", fuse_fast=False, flags=None):
+    """[([(nonce, hash), ...], (hash, nonce), scanned, path), ...] of many (msg, lower, upper, target,
+    k) requests: entries and (hash, nonce) exactly what search_first_hits() gives for each, with the
+    small ones fused into one GPU pass whose tiles stop at their request's own bound
+    (mh_search_first_hits_batch).  fuse_fast=True also fuses the fast pieces of the larger requests,
+    up to MH_BATCH_FAST_MAX_NONCES nonces each (MH_BATCH_FUSE_FAST; `flags` overrides the flag word).
+    path: 0 answered from the fused pass, 1 fallback, 2 fused and then rebuilt through the
+    search_first_hits path.  Per-request failures as search_batch: raised with the request's index,
+    or with errors="return" left in place in the list."""
+    if errors not in ("raise", "return"):
+        raise ValueError(f"errors = {errors!r}: expected 'raise' or 'return'")
+    requests = list(requests)
+    arr, keep, offsets, total = _first_hits_requests(requests)
+    buf = np.empty((max(1, total), 2), dtype=np.uint64)
+    out = (mh_first_hits_result * max(1, len(requests)))()
+    hits = buf.ctypes.data_as(ctypes.POINTER(mh_hit)) if total else None
+    word = (MH_BATCH_FUSE_FAST if fuse_fast else 0) if flags is None else flags
+    _check(lib.mh_search_first_hits_batch(dev, arr, len(requests), word, hits, total, out))
+    res = []
+    for i in range(len(requests)):
+        o = out[i]
+        if o.status == MH_OK:
+            assert o.offset == offsets[i]
+            entries = [(n, h) for h, n in buf[o.offset:o.offset + o.stored].tolist()] if o.stored else []
+            res.append((entries, (o.hash, o.nonce), o.scanned, o.path))
+            continue
+        what = ("k is 0" if o.status == MH_EINVAL and arr[i].k == 0
+                else "k is larger than MH_HITS_MAX_CAP" if o.status == MH_EINVAL and arr[i].k > MH_HITS_MAX_CAP
+                else _REQUEST_ERRORS.get(o.status, "failed"))
+        e = MinehipError(o.status, f"request {i}: {what}")
+        e.index = i
+        if errors == "raise":
+            raise e
+        res.append(e)
+    return res
+
+
+def first_hits_batch_regions(requests, fuse_fast=False, flags=None):
+    """Host-only: how search_first_hits_batch would run the requests -- hits_batch_regions' dicts
+    with the regions of that call: a request of k wants min(its nonce count, max(4 k, 256)) entries
+    (mh_first_hits_batch_regions; kind and pass follow batch_plan_ex with the same flags)."""
+    requests = list(requests)
+    arr, keep, _, _ = _first_hits_requests(requests)
+    buf = (mh_hits_region * max(1, len(requests)))()
+    word = (MH_BATCH_FUSE_FAST if fuse_fast else 0) if flags is None else flags
+    k = lib.mh_first_hits_batch_regions(arr, len(requests), word, buf, len(requests))
     if k < 0:
         _check(k)
     return [{f: getattr(buf[i], f) for f, _ in mh_hits_region._fields_ if f != "reserved"} for i in range(k)]

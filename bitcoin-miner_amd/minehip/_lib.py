@@ -44,6 +44,7 @@ EXPORTS = (
     "mh_search_first_batch_ex", "mh_first_batch_order_ex", "mh_search_hits_batch_ex", "mh_hits_batch_regions_ex",
     "mh_miner_handle_batch_ex", "mh_search_first_ex", "mh_search_first_batch_stop",
     "mh_search_first_hits", "mh_first_hits_slices", "mh_first_hits_bound",
+    "mh_search_first_hits_batch", "mh_first_hits_batch_regions",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -119,6 +120,17 @@ class mh_hits_request(ctypes.Structure):
 class mh_hits_result(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("count", ctypes.c_uint64),
                 ("stored", ctypes.c_uint64), ("hash", ctypes.c_uint64), ("nonce", ctypes.c_uint64),
+                ("offset", ctypes.c_uint64)]
+
+
+class mh_first_hits_request(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t), ("lower", ctypes.c_uint64),
+                ("upper", ctypes.c_uint64), ("target", ctypes.c_uint64), ("k", ctypes.c_uint64)]
+
+
+class mh_first_hits_result(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("path", ctypes.c_int32), ("stored", ctypes.c_uint64),
+                ("scanned", ctypes.c_uint64), ("hash", ctypes.c_uint64), ("nonce", ctypes.c_uint64),
                 ("offset", ctypes.c_uint64)]
 
 
@@ -233,6 +245,10 @@ def _load():
                                            ctypes.POINTER(mh_hits_region), ctypes.c_int64]
     L.mh_hits_batch_regions.argtypes = [ctypes.POINTER(mh_hits_request), sz, ctypes.POINTER(mh_hits_region),
                                         ctypes.c_int64]
+    L.mh_search_first_hits_batch.argtypes = [ctypes.c_int, ctypes.POINTER(mh_first_hits_request), sz, ctypes.c_uint32,
+                                             ctypes.POINTER(mh_hit), sz, ctypes.POINTER(mh_first_hits_result)]
+    L.mh_first_hits_batch_regions.argtypes = [ctypes.POINTER(mh_first_hits_request), sz, ctypes.c_uint32,
+                                              ctypes.POINTER(mh_hits_region), ctypes.c_int64]
     L.mh_batch_plan.argtypes = [ctypes.POINTER(mh_request), sz, ctypes.POINTER(mh_batch_item), ctypes.c_int64]
     L.mh_search_batch_ex.argtypes = [ctypes.c_int, ctypes.POINTER(mh_request), sz, ctypes.c_uint32,
                                      ctypes.POINTER(mh_result)]
@@ -269,6 +285,7 @@ def _load():
                "mh_batch_plan_ex": ctypes.c_int64,
                "mh_first_batch_order": ctypes.c_int64, "mh_hits_batch_regions": ctypes.c_int64,
                "mh_first_batch_order_ex": ctypes.c_int64, "mh_hits_batch_regions_ex": ctypes.c_int64,
+               "mh_first_hits_batch_regions": ctypes.c_int64,
                "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
                "mh_sched_create_ex": vp, "mh_server_create_ex": vp, "mh_sched_default_queue_opts": None,

@@ -95,6 +95,15 @@ def hits_stop_code_object():
     return ctypes.string_at(b, e - b)
 
 
+def batch_bound_code_object():
+    """The embedded code object of the stopping hits batch kernels (mh_search_first_hits_batch):
+    batch_bound<J, MODE>, fast_search.hip built with -DMH_BATCH -DMH_HITS -DMH_STOP
+    (mh_batch_bound_co_begin .. mh_batch_bound_co_end)."""
+    b = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_bound_co_begin"))
+    e = ctypes.addressof(ctypes.c_ubyte.in_dll(lib, "mh_batch_bound_co_end"))
+    return ctypes.string_at(b, e - b)
+
+
 def unpack_msgpack(b):
     """Decode one MessagePack object (the subset AMDGPU metadata uses: maps, arrays, strings,
     binary, integers, floats, booleans, nil).  No dependency on the msgpack package."""
@@ -238,3 +247,9 @@ def batch_hits_kernel_resources(co=None):
     """The same of the embedded batch_hits<J, MODE> kernels (or of those of code object `co`)."""
     return fast_kernel_resources(batch_hits_code_object() if co is None else co,
                                  r"_ZN2mh10batch_hitsILi(\d+)ELi(\d+)E")
+
+
+def batch_bound_kernel_resources(co=None):
+    """The same of the embedded batch_bound<J, MODE> kernels (or of those of code object `co`)."""
+    return fast_kernel_resources(batch_bound_code_object() if co is None else co,
+                                 r"_ZN2mh11batch_boundILi(\d+)ELi(\d+)E")

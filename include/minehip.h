@@ -337,7 +337,8 @@ typedef struct mh_first_hits {
  * Errors, before any device is touched: MH_EINVAL for out == NULL, hits == NULL, k == 0 or
  * k > MH_HITS_MAX_CAP; MH_ERANGE, MH_ETOOLONG and MH_EINVAL for a NULL msg with len > 0, as
  * mh_search; then MH_ENODEV.  The dev build refuses the hash and code-object hooks as
- * mh_search_hits does.  One device only, no batched form, nothing in the LSP protocol or the miner.
+ * mh_search_hits does.  One device only; the batched form is mh_search_first_hits_batch below;
+ * nothing in the LSP protocol or the miner.
  * Additive in ABI 5 (no existing struct or function changes). */
 int mh_search_first_hits(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                          uint64_t target, mh_hit *hits, size_t k, mh_first_hits *out);
@@ -426,6 +427,60 @@ int mh_search_hits_batch(int dev, const mh_hits_request *reqs, size_t n, mh_hit 
  * MH_BATCH_FAST_MAX_NONCES.  Additive in ABI 5. */
 int mh_search_hits_batch_ex(int dev, const mh_hits_request *reqs, size_t n, uint32_t flags, mh_hit *hits,
                             size_t hits_cap, mh_hits_result *out);
+
+/* ---- batched first k hits: the k smallest hits of many Requests ---------- */
+
+typedef struct mh_first_hits_request {
+    const uint8_t *msg;
+    size_t len;
+    uint64_t lower, upper, target;
+    uint64_t k; /* entries wanted for this request, 1 .. MH_HITS_MAX_CAP */
+} mh_first_hits_request; /* 48 bytes */
+
+typedef struct mh_first_hits_result {
+    int32_t status; /* MH_OK, or the MH_E* of this request alone (the other fields are then 0, but offset) */
+    int32_t path;   /* 0 answered from the fused pass; 1 fallback (never fused); 2 fused, then rebuilt
+                       through the mh_search_first_hits path */
+    uint64_t stored, scanned, hash, nonce; /* exactly mh_first_hits' fields */
+    uint64_t offset; /* this request's entries are hits[offset .. offset + stored) */
+} mh_first_hits_result; /* 48 bytes */
+
+/* mh_search_first_hits for n requests on one device.  For every request whose status is MH_OK,
+ * stored, hash, nonce and the `stored` entries at hits + offset are bit for bit what
+ * mh_search_first_hits(dev, msg, len, lower, upper, target, hits + offset, k, ...) returns; they do
+ * not depend on the batch's contents, the packing into passes, the dispatch order
+ * (MINEHIP_FIRST_BATCH_ORDER), the fused / fallback / rebuilt split, MINEHIP_HITS_SLOTS,
+ * MINEHIP_BATCH_SLOTS or timing.  Only scanned and path may: with stored < k, scanned ==
+ * upper - lower + 1; with stored == k, hits[k-1].nonce - lower + 1 <= scanned <= upper - lower + 1.
+ * offset of request i is the sum of k over requests 0 .. i-1 whatever their status, a k of 0 or
+ * above MH_HITS_MAX_CAP counting as 0 (mh_search_hits_batch's rule for cap).  hits holds hits_cap
+ * entries.
+ * flags == 0 fuses the requests whose plan holds only generic pieces (mh_batch_plan's split);
+ * MH_BATCH_FUSE_FAST (the only flag; any other bit: MH_EINVAL before a device is touched) also
+ * fuses requests with fast pieces exactly as mh_batch_plan_ex decides it (the same cap,
+ * MH_BATCH_FAST_MAX_NONCES, and lane rule).  The plan depends on neither targets nor k.
+ * A fused request has one set of device words in its pass's tables -- target, cursor, region, k,
+ * bound, the slicing of its own range (mh_first_hits_slices, mh_first_hits_bound) and the scanned
+ * count -- and 1,024 slice counters of its own.  Its generic tiles (batch_scan_bound, taken in
+ * mh_first_batch_order_ex's rank-major order) and the chunks of its fast pieces (batch_bound<J, MODE>)
+ * append through its cursor into its region of the device hit buffer, count every hit in its slices
+ * before the cursor advances, publish its bound once the slices hold k hits, and skip a tile or chunk
+ * -- or leave a running chunk at its next group of ten nonces -- that lies wholly above its bound.  A
+ * request's bound stops that request's work and no other's.  Nothing waits on a word.
+ * A request gets min(its nonce count, max(4 k, 256), what the window has left) entries of the device
+ * hit buffer (mh_first_hits_batch_regions shows the schedule); windows and drains are
+ * mh_search_hits_batch's, and a batch whose wants fit one window has one host synchronise.  A fused
+ * request that appended more hits than its region holds (path 2) and a fallback (path 1) run through
+ * the mh_search_first_hits path after the fused passes.
+ * Per-request failures go to out[i].status and do not stop the others: MH_ERANGE, MH_ETOOLONG,
+ * MH_EINVAL (msg NULL with len > 0, k == 0 or k > MH_HITS_MAX_CAP).  For the call: MH_EINVAL for
+ * NULL reqs or out with n > 0, for the sum of k (as counted for offset) above hits_cap, and for
+ * hits == NULL with that sum above 0; n == 0 returns MH_OK without touching a device; a
+ * device-level failure (MH_ENODEV, MH_EHIP, MH_EINTERNAL) is the call's return code and leaves out
+ * undefined.  The dev build refuses the hash and code-object hooks as mh_search_first_hits does.
+ * One device only; nothing in the LSP protocol or the miner.  Additive in ABI 5. */
+int mh_search_first_hits_batch(int dev, const mh_first_hits_request *reqs, size_t n, uint32_t flags,
+                               mh_hit *hits, size_t hits_cap, mh_first_hits_result *out);
 
 /* Thread-local description of the calling thread's last failure ("" if none). */
 const char *mh_last_error(void);
@@ -629,6 +684,14 @@ int64_t mh_hits_batch_regions(const mh_hits_request *reqs, size_t n, mh_hits_reg
  * of its pieces, kind 1 for a fallback. */
 int64_t mh_hits_batch_regions_ex(const mh_hits_request *reqs, size_t n, uint32_t flags, mh_hits_region *out,
                                  int64_t cap);
+
+/* Host only: how mh_search_first_hits_batch(flags) would run reqs[0..n): mh_hits_batch_regions_ex's
+ * items with the regions of that call -- a request of k wants min(its nonce count, max(4 k, 256))
+ * entries and gets min(that, what the window has left).  kind and pass follow mh_batch_plan_ex(flags).
+ * Honours MINEHIP_HITS_SLOTS and MINEHIP_BATCH_SLOTS.  The return values are mh_hits_batch_regions';
+ * the first request the call would refuse (k == 0 included) gives its MH_E*. */
+int64_t mh_first_hits_batch_regions(const mh_first_hits_request *reqs, size_t n, uint32_t flags,
+                                    mh_hits_region *out, int64_t cap);
 
 /* One span of mh_search_multi's adaptive split (chunk == 0), ABI 4. */
 typedef struct mh_span {
