@@ -1,7 +1,7 @@
 // batch.cpp -- the batched entry points of libminehip.so's C-ABI (declared in include/minehip.h):
 // mh_search_batch[_ex], mh_search_first_batch[_ex], mh_search_first_batch_stop,
 // mh_search_hits_batch[_ex], mh_search_first_hits_batch, their host-only plan probes,
-// mh_miner_handle_batch[_ex] and mh_hash_batch.
+// mh_miner_handle, mh_miner_handle_batch[_ex] and mh_hash_batch.
 //
 // A batch fuses its small requests into passes on the device's one stream: per pass one H2D copy
 // of its tables, the scan of the generic entries, one fast launch per layout present, a merge and
@@ -1591,6 +1591,35 @@ int64_t mh_first_hits_batch_regions(const mh_first_hits_request* reqs, size_t n,
     return k;
 }
 
+int mh_miner_handle(const int* devs, int ndev, const char* request, size_t len, char* out, size_t cap,
+                    size_t* out_len) {
+    if (!request || !devs || ndev <= 0) return fail(MH_EINVAL, "bad arguments");
+    mh::Msg m;
+    if (!mh::decode(request, len, &m)) return fail(MH_ENOTREQ, "payload is not a JSON bitcoin.Message");
+    if (m.type != 1) return fail(MH_ENOTREQ, "not a Request");  // message.go:10
+    if (m.lower > m.upper) return fail(MH_ERANGE, "lower > upper");
+    const uint8_t* d = (const uint8_t*)m.data.data();
+    uint64_t h = 0, n = 0;
+    if (m.has_target) {  // a chunk of a target job (minehip_server.h): the chunk's first hit, else its minimum
+        mh_first f;
+        const int rc = (ndev == 1)
+                           ? mh_search_first_ex(devs[0], d, m.data.size(), m.lower, m.upper, m.target, 0u, &f)
+                           : mh_search_first_multi(devs, ndev, d, m.data.size(), m.lower, m.upper, m.target, 0, 0u, &f);
+        if (rc) return rc;
+        h = f.hash;
+        n = f.nonce;
+    } else {
+        const int rc = (ndev == 1) ? mh_search(devs[0], d, m.data.size(), m.lower, m.upper, &h, &n)
+                                   : mh_search_multi(devs, ndev, d, m.data.size(), m.lower, m.upper, 0, &h, &n);
+        if (rc) return rc;
+    }
+    const std::string s = mh::encode(2, nullptr, 0, 0, 0, h, n);  // NewResult (message.go:38-44)
+    if (out_len) *out_len = s.size();
+    if (!out || cap < s.size()) return fail(MH_EINVAL, "output buffer too small");
+    memcpy(out, s.data(), s.size());
+    return MH_OK;
+}
+
 int mh_miner_handle_batch(const int* devs, int ndev, const char* const* requests, const size_t* lens, size_t n,
                           char* out, size_t cap_each, size_t* out_lens, int* status) {
     return mh_miner_handle_batch_ex(devs, ndev, requests, lens, n, 0, out, cap_each, out_lens, status);
@@ -1605,6 +1634,8 @@ int mh_miner_handle_batch_ex(const int* devs, int ndev, const char* const* reque
     std::vector<mh::Msg> msgs(n);
     std::vector<mh_request> reqs;
     std::vector<size_t> where;  // reqs[k] is payload where[k]
+    std::vector<mh_first_request> freqs;  // the Requests with a Target, and their payloads
+    std::vector<size_t> fwhere;
     for (size_t i = 0; i < n; ++i) {
         if (out_lens) out_lens[i] = 0;
         mh::Msg& m = msgs[i];
@@ -1616,10 +1647,34 @@ int mh_miner_handle_batch_ex(const int* devs, int ndev, const char* const* reque
             status[i] = fail(MH_ENOTREQ, "not a Request");  // message.go:10
         } else if (m.lower > m.upper) {
             status[i] = fail(MH_ERANGE, "lower > upper");
+        } else if (m.has_target) {
+            status[i] = MH_OK;
+            freqs.push_back(mh_first_request{(const uint8_t*)m.data.data(), m.data.size(), m.lower, m.upper, m.target});
+            fwhere.push_back(i);
         } else {
             status[i] = MH_OK;
             reqs.push_back(mh_request{(const uint8_t*)m.data.data(), m.data.size(), m.lower, m.upper});
             where.push_back(i);
+        }
+    }
+    // NewResult (message.go:38-44) of payload i
+    auto put = [&](size_t i, uint64_t hash, uint64_t nonce) {
+        const std::string s = mh::encode(2, nullptr, 0, 0, 0, hash, nonce);
+        if (out_lens) out_lens[i] = s.size();
+        if (!out || cap_each < s.size()) {
+            status[i] = fail(MH_EINVAL, "output buffer too small");
+            return;
+        }
+        memcpy(out + i * cap_each, s.data(), s.size());
+    };
+    if (!freqs.empty()) {
+        // the Target Requests: one first-hit batch on devs[0], answered as mh_miner_handle answers each
+        std::vector<mh_first_result> fres(freqs.size());
+        const int rc = mh_search_first_batch_ex(devs[0], freqs.data(), freqs.size(), flags, fres.data());
+        if (rc) return rc;
+        for (size_t k = 0; k < freqs.size(); ++k) {
+            status[fwhere[k]] = fres[k].status;
+            if (fres[k].status == MH_OK) put(fwhere[k], fres[k].hash, fres[k].nonce);
         }
     }
     if (reqs.empty()) return MH_OK;
@@ -1639,13 +1694,7 @@ int mh_miner_handle_batch_ex(const int* devs, int ndev, const char* const* reque
         const size_t i = where[k];
         status[i] = res[k].status;
         if (res[k].status) continue;
-        const std::string s = mh::encode(2, nullptr, 0, 0, 0, res[k].hash, res[k].nonce);  // NewResult (message.go:38-44)
-        if (out_lens) out_lens[i] = s.size();
-        if (!out || cap_each < s.size()) {
-            status[i] = fail(MH_EINVAL, "output buffer too small");
-            continue;
-        }
-        memcpy(out + i * cap_each, s.data(), s.size());
+        put(i, res[k].hash, res[k].nonce);
     }
     return MH_OK;
 }

@@ -1,4 +1,5 @@
-// message.cpp -- the miner process's wire format and request handler.
+// message.cpp -- the miner process's wire format (its request handler, mh_miner_handle, is in
+// batch.cpp beside its batched forms: this file needs no search).
 //
 // Reference: bitcoin/message.go:18-23 (Message{Type, Data, Lower, Upper,
 // Hash, Nonce}), :7-13 (Join=0, Request=1, Result=2), :27-49 (NewRequest /
@@ -311,6 +312,9 @@ bool decode(const char* js, size_t len, Msg* m) {
                 ok = p.u64(&m->hash);
             } else if (key_is(k, "Nonce")) {
                 ok = p.u64(&m->nonce);
+            } else if (key_is(k, "Target")) {
+                ok = p.u64(&m->target);
+                if (ok) m->has_target = true;
             } else {
                 ok = p.skip_value();
             }
@@ -340,6 +344,16 @@ std::string encode(int64_t type, const uint8_t* data, size_t dlen, uint64_t lowe
     return o;
 }
 
+std::string encode(int64_t type, const uint8_t* data, size_t dlen, uint64_t lower, uint64_t upper, uint64_t hash,
+                   uint64_t nonce, bool has_target, uint64_t target) {
+    std::string o = encode(type, data, dlen, lower, upper, hash, nonce);
+    if (has_target) {
+        o.pop_back();
+        o += ",\"Target\":" + std::to_string(target) + "}";
+    }
+    return o;
+}
+
 }  // namespace mh
 
 namespace {
@@ -365,6 +379,12 @@ int mh_msg_encode(int64_t type, const uint8_t* data, size_t dlen, uint64_t lower
     return copy_out(encode(type, data, dlen, lower, upper, hash, nonce), out, cap, out_len);
 }
 
+int mh_msg_encode_ex(int64_t type, const uint8_t* data, size_t dlen, uint64_t lower, uint64_t upper, uint64_t hash,
+                     uint64_t nonce, int has_target, uint64_t target, char* out, size_t cap, size_t* out_len) {
+    if (!data && dlen) return mh::set_error(MH_EINVAL, "data is NULL");
+    return copy_out(encode(type, data, dlen, lower, upper, hash, nonce, has_target != 0, target), out, cap, out_len);
+}
+
 int mh_msg_decode(const char* json, size_t len, mh_message* out, uint8_t* data, size_t data_cap) {
     if (!json || !out) return mh::set_error(MH_EINVAL, "NULL argument");
     Msg m;
@@ -381,20 +401,23 @@ int mh_msg_decode(const char* json, size_t len, mh_message* out, uint8_t* data, 
     return MH_OK;
 }
 
-int mh_miner_handle(const int* devs, int ndev, const char* request, size_t len, char* out, size_t cap,
-                    size_t* out_len) {
-    if (!request || !devs || ndev <= 0) return mh::set_error(MH_EINVAL, "bad arguments");
+int mh_msg_decode_ex(const char* json, size_t len, mh_message_ex* out, uint8_t* data, size_t data_cap) {
+    if (!json || !out) return mh::set_error(MH_EINVAL, "NULL argument");
     Msg m;
-    if (!decode(request, len, &m)) return mh::set_error(MH_ENOTREQ, "payload is not a JSON bitcoin.Message");
-    if (m.type != 1) return mh::set_error(MH_ENOTREQ, "not a Request");  // message.go:10
-    if (m.lower > m.upper) return mh::set_error(MH_ERANGE, "lower > upper");
-    uint64_t h = 0, n = 0;
-    const int rc = (ndev == 1)
-                       ? mh_search(devs[0], (const uint8_t*)m.data.data(), m.data.size(), m.lower, m.upper, &h, &n)
-                       : mh_search_multi(devs, ndev, (const uint8_t*)m.data.data(), m.data.size(), m.lower, m.upper,
-                                         0, &h, &n);
-    if (rc) return rc;
-    return copy_out(encode(2, nullptr, 0, 0, 0, h, n), out, cap, out_len);  // NewResult (message.go:38-44)
+    if (!decode(json, len, &m)) return mh::set_error(MH_EINVAL, "payload is not a JSON bitcoin.Message");
+    out->type = m.type;
+    out->lower = m.lower;
+    out->upper = m.upper;
+    out->hash = m.hash;
+    out->nonce = m.nonce;
+    out->data_len = m.data.size();
+    out->has_target = m.has_target ? 1 : 0;
+    out->reserved = 0;
+    out->target = m.has_target ? m.target : 0;
+    if (m.data.size() > data_cap || (!data && !m.data.empty()))
+        return mh::set_error(MH_ETOOLONG, "data buffer too small");
+    if (!m.data.empty()) memcpy(data, m.data.data(), m.data.size());
+    return MH_OK;
 }
 
 }  // extern "C"

@@ -876,6 +876,29 @@ uint64_t mh_first_hits_bound(uint64_t lower, uint64_t upper, uint64_t k, const u
     return mh::first_hits_bound(lower, upper - lower, mh::first_hits_shift(upper - lower), k, counts);
 }
 
+// The test hooks of the multi-device coordinators, dev build only (`make dev`, -DMH_DEV_HOOKS):
+// MINEHIP_TEST_FAIL_WORKER=i makes worker i's searches fail with MH_EHIP, to exercise the
+// hand-back path on a one-GPU box; MINEHIP_TEST_SPAWN_LIMIT=k makes the host thread of every worker
+// after the first k fail to start (std::system_error, as when the process is out of threads), so
+// the start-failure path of the coordinators runs on any box.
+static void multi_test_hooks(int* fail_worker, mh::ThreadStart* start) {
+#ifdef MH_DEV_HOOKS
+    if (const char* e = getenv("MINEHIP_TEST_FAIL_WORKER")) *fail_worker = atoi(e);
+    if (const char* e = getenv("MINEHIP_TEST_SPAWN_LIMIT")) {
+        auto started = std::make_shared<std::atomic<int>>(0);
+        const int limit = atoi(e);
+        *start = [started, limit](std::function<void()> fn) {
+            if ((*started)++ >= limit)
+                throw std::system_error(std::make_error_code(std::errc::resource_unavailable_try_again));
+            return std::thread(std::move(fn));
+        };
+    }
+#else
+    (void)fail_worker;
+    (void)start;
+#endif
+}
+
 int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
                     uint64_t chunk, uint64_t* out_hash, uint64_t* out_nonce) {
     g_err.clear();
@@ -889,28 +912,11 @@ int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, u
         if (devs[i] < 0 || devs[i] >= n) return fail(n <= 0 ? MH_ENODEV : MH_EINVAL, "device index out of range");
     mh::Prefix pre;
     mh::absorb_prefix(msg, len, &pre);
+    int fail_worker = -1;
+    mh::ThreadStart start;
+    multi_test_hooks(&fail_worker, &start);
     // One device and adaptive chunks: nothing to balance, so one search (one
     // plan, full-size launches) instead of a chain of shrinking chunks.
-    // test hook of the dev build only (`make dev`, -DMH_DEV_HOOKS):
-    // MINEHIP_TEST_FAIL_WORKER=i makes worker i's first search fail with
-    // MH_EHIP, to exercise the hand-back path on a one-GPU box
-    int fail_worker = -1;
-    // MINEHIP_TEST_SPAWN_LIMIT=k (dev build only): the host thread of every worker after the first
-    // k fails to start (std::system_error, as when the process is out of threads), so the
-    // start-failure path of both coordinators runs on any box
-    mh::ThreadStart start;
-#ifdef MH_DEV_HOOKS
-    if (const char* e = getenv("MINEHIP_TEST_FAIL_WORKER")) fail_worker = atoi(e);
-    if (const char* e = getenv("MINEHIP_TEST_SPAWN_LIMIT")) {
-        auto started = std::make_shared<std::atomic<int>>(0);
-        const int limit = atoi(e);
-        start = [started, limit](std::function<void()> fn) {
-            if ((*started)++ >= limit)
-                throw std::system_error(std::make_error_code(std::errc::resource_unavailable_try_again));
-            return std::thread(std::move(fn));
-        };
-    }
-#endif
     if (ndev == 1 && chunk == 0 && fail_worker < 0 && !start)
         return search_impl(devs[0], pre, lower, upper, out_hash, out_nonce);
     // Adaptive: one rate-weighted shard per device (+ a short dynamic tail on long ranges), multi.hpp.
@@ -940,6 +946,57 @@ int mh_search_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, u
     std::string err;
     const int r = mh::search_chunks(ndev, msg, len, lower, upper, chunk, csearch, out_hash, out_nonce, &err, start);
     return r ? fail(r, err) : MH_OK;
+}
+
+int mh_search_first_multi(const int* devs, int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                          uint64_t target, uint64_t chunk, uint32_t flags, mh_first* out) {
+    g_err.clear();
+    if (flags & ~MH_FIRST_STOP_RUNNING) return fail(MH_EINVAL, "unknown flag bit");
+    if (!out || !devs || ndev <= 0) return fail(MH_EINVAL, "bad arguments");
+    if (ndev > MH_MAX_WORKERS) return fail(MH_EINVAL, "more than MH_MAX_WORKERS devices listed");
+    int rc = check_common(msg, len);
+    if (rc) return rc;
+    if (lower > upper) return fail(MH_ERANGE, "lower > upper");
+    rc = refuse_hash_hooks("mh_search_first_multi");
+    if (rc) return rc;
+    const int n = mh_device_count();
+    for (int i = 0; i < ndev; ++i)
+        if (devs[i] < 0 || devs[i] >= n) return fail(n <= 0 ? MH_ENODEV : MH_EINVAL, "device index out of range");
+    mh::Prefix pre;
+    mh::absorb_prefix(msg, len, &pre);
+    int fail_worker = -1;
+    mh::ThreadStart start;
+    multi_test_hooks(&fail_worker, &start);
+    if (chunk == 0) {  // the scheduler's own init_chunk default (2^30); not tuned for this call
+        mh_sched_opts o;
+        mh_sched_default_opts(&o);
+        chunk = o.init_chunk;
+    }
+    // One miner per listed device over a target job of the server's scheduler (multi.cpp
+    // search_first_chunks): each takes the next chunk, in ascending order, and answers it as
+    // mh_miner_handle answers a Request with a Target.
+    const mh::FirstChunkSearch csearch = [&](int worker, uint64_t lo, uint64_t hi, uint64_t* h, uint64_t* nn,
+                                             uint64_t* scanned, std::string* err) {
+        mh_first f{};
+        const int r = (worker == fail_worker) ? fail(MH_EHIP, "injected failure (dev build test hook)")
+                                              : search_first_impl(devs[worker], pre, lo, hi, target, flags, &f);
+        if (r) *err = g_err;
+        *h = f.hash;
+        *nn = f.nonce;
+        *scanned = f.scanned;
+        return r;
+    };
+    std::string err;
+    uint64_t h = 0, nn = 0, scanned = 0;
+    const int r = mh::search_first_chunks(ndev, msg, len, lower, upper, target, chunk, csearch, &h, &nn, &scanned, &err,
+                                          start);
+    if (r) return fail(r, err);
+    out->found = h <= target ? 1 : 0;
+    out->reserved = 0;
+    out->hash = h;
+    out->nonce = nn;
+    out->scanned = scanned;
+    return MH_OK;
 }
 
 int mh_profile_enable(int dev, int on) {

@@ -179,21 +179,27 @@ int search_shards(const int* devs, int ndev, const Prefix& pre, uint64_t lower, 
     return MH_OK;
 }
 
-int search_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t chunk,
-                  const ChunkSearch& search, uint64_t* out_hash, uint64_t* out_nonce, std::string* err,
-                  const ThreadStart& start) {
+namespace {
+
+// search_chunks and search_first_chunks: the job is a plain one, or with `target` a target job, whose
+// completion may come while other workers still run chunks above the hit (their late Results are
+// ignored by the scheduler; their nonces still count in *scanned).
+int run_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t chunk,
+               const uint64_t* target, const FirstChunkSearch& search, uint64_t* out_hash, uint64_t* out_nonce,
+               uint64_t* out_scanned, std::string* err, const ThreadStart& start) {
     mh_sched_opts o;
     mh_sched_default_opts(&o);
     o.init_chunk = o.min_chunk = o.max_chunk = chunk;
     Scheduler sched(o);
     for (int i = 0; i < ndev; ++i) sched.add_miner(i);
-    if (sched.submit(0, msg, len, lower, upper) < 0) {
+    if ((target ? sched.submit_first(0, msg, len, lower, upper, *target) : sched.submit(0, msg, len, lower, upper)) < 0) {
         *err = "internal: submit failed";
         return MH_EINTERNAL;
     }
     std::mutex mu;
     std::condition_variable cv;
     uint64_t gen = 0;  // bumped on every completion or worker loss
+    uint64_t scanned = 0;
     int alive = ndev, first_err = 0;
     bool done = false;
     mh_completion res{};
@@ -217,9 +223,9 @@ int search_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint
                 cv.wait(lk, [&] { return done || gen != seen; });
                 continue;
             }
-            uint64_t h = 0, nn = 0;
+            uint64_t h = 0, nn = 0, sc = 0;
             std::string e;
-            const int r = search(i, a.lower, a.upper, &h, &nn, &e);
+            const int r = search(i, a.lower, a.upper, &h, &nn, &sc, &e);
             if (r) {
                 sched.remove_miner(i);  // its chunk goes back to the job
                 std::lock_guard<std::mutex> lk(mu);
@@ -235,6 +241,7 @@ int search_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint
             mh_completion c;
             const int q = sched.result(i, h, nn, now(), &c);
             std::lock_guard<std::mutex> lk(mu);
+            scanned += sc;
             if (q == 1) {
                 res = c;
                 done = true;
@@ -267,7 +274,26 @@ int search_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint
     }
     *out_hash = res.hash;
     *out_nonce = res.nonce;
+    *out_scanned = scanned;
     return MH_OK;
+}
+
+}  // namespace
+
+int search_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t chunk,
+                  const ChunkSearch& search, uint64_t* out_hash, uint64_t* out_nonce, std::string* err,
+                  const ThreadStart& start) {
+    const FirstChunkSearch s = [&search](int worker, uint64_t lo, uint64_t hi, uint64_t* h, uint64_t* nn, uint64_t*,
+                                         std::string* e) { return search(worker, lo, hi, h, nn, e); };
+    uint64_t scanned = 0;
+    return run_chunks(ndev, msg, len, lower, upper, chunk, nullptr, s, out_hash, out_nonce, &scanned, err, start);
+}
+
+int search_first_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                        uint64_t chunk, const FirstChunkSearch& search, uint64_t* out_hash, uint64_t* out_nonce,
+                        uint64_t* out_scanned, std::string* err, const ThreadStart& start) {
+    return run_chunks(ndev, msg, len, lower, upper, chunk, &target, search, out_hash, out_nonce, out_scanned, err,
+                      start);
 }
 
 }  // namespace mh

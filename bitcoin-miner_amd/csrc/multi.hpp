@@ -73,4 +73,19 @@ int search_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint
                   const ChunkSearch& search, uint64_t* out_hash, uint64_t* out_nonce, std::string* err,
                   const ThreadStart& start = {});
 
+// One first-hit search of [lo, hi] by `worker`: the chunk's smallest nonce with hash <= target and
+// its hash, or its minimum when none qualifies, and the nonces it hashed.
+using FirstChunkSearch = std::function<int(int worker, uint64_t lo, uint64_t hi, uint64_t* hash, uint64_t* nonce,
+                                           uint64_t* scanned, std::string* err)>;
+
+// mh_search_first_multi: search_chunks over a target job of the scheduler (sched.hpp) -- chunks in
+// ascending order, none handed out above a known hit, done once every chunk below the hit is
+// answered; the workers still running a chunk above it finish that chunk before the call returns.
+// The first hit and its hash, or the minimum when nothing qualifies (the caller tells them apart by
+// hash <= target); *out_scanned sums `scanned` over the chunks that completed.  Failures as
+// search_chunks.
+int search_first_chunks(int ndev, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, uint64_t target,
+                        uint64_t chunk, const FirstChunkSearch& search, uint64_t* out_hash, uint64_t* out_nonce,
+                        uint64_t* out_scanned, std::string* err, const ThreadStart& start = {});
+
 }  // namespace mh

@@ -115,17 +115,43 @@ bool Scheduler::eligible(const Miner& m) const {
 }
 
 // A chunk that will not be answered goes back to the front of its job (a cancelled job only
-// counts it off).
+// counts it off).  A target job's requeued chunks stay in ascending order (take cuts from the
+// front: the lowest nonces first), and one that lies above a known hit is not wanted any more; a
+// finished job only counts it off, as a cancelled one does.
 void Scheduler::requeue_chunk(const Chunk& c) {
     Job* j = find_job(c.job);
     if (!j) return;
     j->outstanding -= 1u;
-    if (!j->cancelled) {
+    if (j->cancelled || j->finished) {
+        if (j->outstanding == 0) erase_job(j->id);
+    } else if (!j->first) {
         j->requeue.emplace_front(c.lo, c.hi);
         st_.chunks_requeued += 1u;
-    } else if (j->outstanding == 0) {
-        erase_job(j->id);
+    } else if (!j->hit || c.lo < j->hit_nonce) {
+        auto it = j->requeue.begin();
+        while (it != j->requeue.end() && it->first < c.lo) ++it;
+        j->requeue.insert(it, std::make_pair(c.lo, c.hi));
+        st_.chunks_requeued += 1u;
     }
+}
+
+// A (smaller) hit became known: nothing above it is handed out any more.  The fresh remainder goes
+// (next is already above the hit's chunk), and so do the requeued chunks above the hit.  Chunks are
+// disjoint and the hit lies in an answered one, so every other chunk is wholly below or above it.
+void Scheduler::prune_above_hit(Job& j) {
+    if (!j.exhausted) {
+        fst_.nonces_dropped += j.upper - j.next + 1u;
+        j.exhausted = true;
+    }
+    while (!j.requeue.empty() && j.requeue.back().first > j.hit_nonce) j.requeue.pop_back();
+}
+
+// Does some miner still hold a chunk of j below its hit?
+bool Scheduler::out_below_hit(const Job& j) const {
+    for (const auto& m : miners_)
+        for (const Chunk& c : m.q)
+            if (c.job == j.id && c.lo < j.hit_nonce) return true;
+    return false;
 }
 
 // Miner i is gone: its chunks go back, newest first, so that the oldest ends up at the front.
@@ -153,6 +179,16 @@ int Scheduler::remove_miner(int64_t id) {
 }
 
 int64_t Scheduler::submit(int64_t client, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper) {
+    return submit_job(client, msg, len, lower, upper, false, 0);
+}
+
+int64_t Scheduler::submit_first(int64_t client, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                                uint64_t target) {
+    return submit_job(client, msg, len, lower, upper, true, target);
+}
+
+int64_t Scheduler::submit_job(int64_t client, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                              bool first, uint64_t target) {
     if (!msg && len) return set_error(MH_EINVAL, "msg is NULL");
     if (len > MH_MAX_MSG_LEN) return set_error(MH_ETOOLONG, "message longer than MH_MAX_MSG_LEN");
     if (lower > upper) return set_error(MH_ERANGE, "lower > upper");
@@ -168,6 +204,11 @@ int64_t Scheduler::submit(int64_t client, const uint8_t* msg, size_t len, uint64
     j->outstanding = 0;
     j->best_hash = j->best_nonce = ~0ull;
     j->cancelled = false;
+    j->first = first;
+    j->hit = j->finished = false;
+    j->target = target;
+    j->hit_hash = j->hit_nonce = ~0ull;
+    if (first) fst_.jobs_first += 1u;
     jobs_.push_back(std::move(j));
     return jobs_.back()->id;
 }
@@ -177,7 +218,7 @@ int Scheduler::drop_client(int64_t client) {
     int n = 0;
     std::vector<int64_t> gone;
     for (auto& j : jobs_) {
-        if (j->client != client || j->cancelled) continue;
+        if (j->client != client || j->cancelled || j->finished) continue;  // a finished job only drains
         j->cancelled = true;
         j->exhausted = true;
         j->requeue.clear();
@@ -208,7 +249,7 @@ int Scheduler::next(int64_t miner, uint64_t now_ns, mh_assignment* out) {
     for (size_t k = 0; k < nj; ++k) {
         const size_t idx = (rr_ + k) % nj;
         Job& j = *jobs_[idx];
-        if (j.cancelled) continue;
+        if (j.cancelled || j.finished) continue;
         uint64_t lo, hi;
         if (!take(j, chunk_size(*m, j), &lo, &hi)) continue;
         rr_ = (idx + 1) % nj;
@@ -232,6 +273,15 @@ int Scheduler::job_msg(int64_t job, std::string* out) {
     Job* j = find_job(job);
     if (!j) return set_error(MH_EINVAL, "unknown job");
     *out = j->msg;
+    return MH_OK;
+}
+
+int Scheduler::job_target(int64_t job, bool* has_target, uint64_t* target) {
+    std::lock_guard<std::mutex> lk(mu_);
+    Job* j = find_job(job);
+    if (!j) return set_error(MH_EINVAL, "unknown job");
+    *has_target = j->first;
+    *target = j->first ? j->target : 0;
     return MH_OK;
 }
 
@@ -288,23 +338,40 @@ int Scheduler::result(int64_t miner, uint64_t hash, uint64_t nonce, uint64_t now
     st_.chunks_done += 1u;
     st_.nonces_done += c.hi - c.lo + 1u;  // wraps only for a single 2^64 chunk
     j->outstanding -= 1u;
-    if (!j->cancelled && lex_less(hash, nonce, j->best_hash, j->best_nonce)) {
+    if (j->cancelled || j->finished) {  // a late Result: counted off and ignored
+        if (j->finished) fst_.results_ignored += 1u;
+        if (j->outstanding == 0) erase_job(j->id);
+        return 0;
+    }
+    if (j->first && hash <= j->target) {
+        // a hit: the job keeps the one with the smallest nonce
+        if (!j->hit || nonce < j->hit_nonce) {
+            j->hit = true;
+            j->hit_hash = hash;
+            j->hit_nonce = nonce;
+            prune_above_hit(*j);
+        }
+    } else if (lex_less(hash, nonce, j->best_hash, j->best_nonce)) {
         j->best_hash = hash;
         j->best_nonce = nonce;
     }
-    if (j->outstanding != 0 || (!j->cancelled && (!j->exhausted || !j->requeue.empty()))) return 0;
-    if (j->cancelled) {
-        erase_job(j->id);
+    // Done: every chunk is back -- or, with a hit, every chunk below it (after prune_above_hit the
+    // requeued ones all are); chunks still out above the hit drain like a cancelled job's.
+    if (j->hit ? (!j->requeue.empty() || out_below_hit(*j))
+               : (j->outstanding != 0 || !j->exhausted || !j->requeue.empty()))
         return 0;
-    }
     if (out) {
         out->job = j->id;
         out->client = j->client;
-        out->hash = j->best_hash;
-        out->nonce = j->best_nonce;
+        out->hash = j->hit ? j->hit_hash : j->best_hash;
+        out->nonce = j->hit ? j->hit_nonce : j->best_nonce;
     }
     st_.jobs_done += 1u;
-    erase_job(j->id);
+    if (j->hit) fst_.jobs_found += 1u;
+    if (j->outstanding == 0)
+        erase_job(j->id);
+    else
+        j->finished = true;
     return 1;
 }
 
@@ -315,6 +382,11 @@ void Scheduler::stats(mh_sched_stats* out) {
     out->idle_miners = 0;
     for (const auto& m : miners_) out->idle_miners += m.q.empty() ? 1u : 0u;
     out->jobs = jobs_.size();
+}
+
+void Scheduler::first_stats(mh_sched_first_stats* out) {
+    std::lock_guard<std::mutex> lk(mu_);
+    *out = fst_;
 }
 
 bool Scheduler::idle_jobs() {
@@ -373,6 +445,22 @@ int64_t mh_sched_submit(mh_sched* s, int64_t client, const uint8_t* msg, size_t 
     return s->s.submit(client, msg, len, lower, upper);
 }
 
+int64_t mh_sched_submit_first(mh_sched* s, int64_t client, const uint8_t* msg, size_t len, uint64_t lower,
+                              uint64_t upper, uint64_t target) {
+    MH_NEED(s);
+    return s->s.submit_first(client, msg, len, lower, upper, target);
+}
+
+int mh_sched_job_target(mh_sched* s, int64_t job, int* has_target, uint64_t* target) {
+    MH_NEED(s);
+    if (!has_target || !target) return mh::set_error(MH_EINVAL, "NULL output");
+    bool has = false;
+    const int rc = s->s.job_target(job, &has, target);
+    if (rc) return rc;
+    *has_target = has ? 1 : 0;
+    return MH_OK;
+}
+
 int mh_sched_drop_client(mh_sched* s, int64_t client) {
     MH_NEED(s);
     return s->s.drop_client(client);
@@ -419,6 +507,13 @@ int mh_sched_stats_read(mh_sched* s, mh_sched_stats* out) {
     MH_NEED(s);
     if (!out) return mh::set_error(MH_EINVAL, "NULL output");
     s->s.stats(out);
+    return MH_OK;
+}
+
+int mh_sched_first_stats_read(mh_sched* s, mh_sched_first_stats* out) {
+    MH_NEED(s);
+    if (!out) return mh::set_error(MH_EINVAL, "NULL output");
+    s->s.first_stats(out);
     return MH_OK;
 }
 

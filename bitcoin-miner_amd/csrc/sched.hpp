@@ -18,6 +18,12 @@
 // chunk; with depth > 1 it is checked against the host Hash given to
 // set_queue, and a miner that fails the check is removed (its later Results
 // would be credited to the wrong chunks).
+//
+// A target job (submit_first) asks the proof-of-work question instead: the smallest nonce whose
+// hash is <= target.  Its chunks go out in ascending order, a Result with hash <= target is a hit,
+// nothing above the smallest known hit b is handed out, and the job is done once no chunk below b
+// is pending or out; chunks still out above b drain as a cancelled job's do (minehip_server.h has
+// the rules, DESIGN.md §7 the argument).  A job from submit() takes none of these paths.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -50,6 +56,9 @@ class Scheduler {
     int add_miner(int64_t id);
     int remove_miner(int64_t id);
     int64_t submit(int64_t client, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper);
+    int64_t submit_first(int64_t client, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper,
+                         uint64_t target);
+    int job_target(int64_t job, bool* has_target, uint64_t* target);
     int drop_client(int64_t client);
     int next(int64_t miner, uint64_t now_ns, mh_assignment* out);
     int job_msg(int64_t job, std::string* out);
@@ -57,6 +66,7 @@ class Scheduler {
     int miner_queue(int64_t miner, std::vector<mh_assignment>* out);
     int result(int64_t miner, uint64_t hash, uint64_t nonce, uint64_t now_ns, mh_completion* out);
     void stats(mh_sched_stats* out);
+    void first_stats(mh_sched_first_stats* out);
     // true when no live job is left (all done or cancelled and drained)
     bool idle_jobs();
 
@@ -72,6 +82,10 @@ class Scheduler {
         uint64_t outstanding;
         uint64_t best_hash, best_nonce;
         bool cancelled;
+        // a target job: first; hit once some Result had hash <= target, (hit_hash, hit_nonce) the one
+        // with the smallest nonce; finished: completed while chunks above the hit are still out
+        bool first, hit, finished;
+        uint64_t target, hit_hash, hit_nonce;
         u128 pending() const;  // nonces not handed out (fresh + requeued)
     };
     struct Chunk {
@@ -95,6 +109,10 @@ class Scheduler {
     bool take(Job& j, uint64_t c, uint64_t* lo, uint64_t* hi);
     bool eligible(const Miner& m) const;
     void requeue_chunk(const Chunk& c);
+    int64_t submit_job(int64_t client, const uint8_t* msg, size_t len, uint64_t lower, uint64_t upper, bool first,
+                       uint64_t target);
+    void prune_above_hit(Job& j);
+    bool out_below_hit(const Job& j) const;
     void drop_miner(size_t i);
 
     std::mutex mu_;
@@ -106,6 +124,7 @@ class Scheduler {
     size_t rr_ = 0;                           // round-robin cursor into jobs_
     int64_t next_job_ = 0;
     mh_sched_stats st_{};
+    mh_sched_first_stats fst_{};
 };
 
 }  // namespace mh

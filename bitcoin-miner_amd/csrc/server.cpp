@@ -10,7 +10,8 @@
 //   Request (message.go:27)  -> a job for the connection (a client);
 //   Result (message.go:38)   -> the miner's chunk is done;
 // and every idle miner is handed a chunk as a Request carrying the job's
-// Data.  A finished job writes NewResult(hash, nonce) to its client.
+// Data.  A finished job writes NewResult(hash, nonce) to its client.  A Request
+// with a Target is a target job: its chunks carry the Target, its Result is plain.
 #include <string.h>
 
 #include <deque>
@@ -40,7 +41,12 @@ struct mh_server {
             std::string m;
             const int rc = s.job_msg(a.job, &m);
             if (rc) return rc;
-            out.emplace_back(a.miner, mh::encode(1, (const uint8_t*)m.data(), m.size(), a.lower, a.upper, 0, 0));
+            bool has_target = false;
+            uint64_t target = 0;
+            const int tc = s.job_target(a.job, &has_target, &target);
+            if (tc) return tc;
+            out.emplace_back(a.miner, mh::encode(1, (const uint8_t*)m.data(), m.size(), a.lower, a.upper, 0, 0,
+                                                 has_target, target));
         }
     }
 };
@@ -105,7 +111,9 @@ int mh_server_read(mh_server* v, int64_t conn, const char* payload, size_t len, 
             if (rc == MH_OK) v->miners.insert(conn);
             break;
         case 1: {  // Request from a client
-            const int64_t id = v->s.submit(conn, (const uint8_t*)m.data.data(), m.data.size(), m.lower, m.upper);
+            const uint8_t* d = (const uint8_t*)m.data.data();
+            const int64_t id = m.has_target ? v->s.submit_first(conn, d, m.data.size(), m.lower, m.upper, m.target)
+                                            : v->s.submit(conn, d, m.data.size(), m.lower, m.upper);
             if (id < 0)  // nothing will ever answer it: the transport closes the client (Disconnected)
                 rc = mh::set_error(MH_EREJECTED, id == MH_ERANGE ? "Request refused: Lower > Upper"
                                                                  : "Request refused: Data too long");
@@ -161,6 +169,12 @@ int mh_server_pop_write(mh_server* v, int64_t* conn, char* out, size_t cap, size
 int mh_server_stats(mh_server* v, mh_sched_stats* out) {
     if (!v || !out) return mh::set_error(MH_EINVAL, "bad arguments");
     v->s.stats(out);
+    return MH_OK;
+}
+
+int mh_server_first_stats(mh_server* v, mh_sched_first_stats* out) {
+    if (!v || !out) return mh::set_error(MH_EINVAL, "bad arguments");
+    v->s.first_stats(out);
     return MH_OK;
 }
 

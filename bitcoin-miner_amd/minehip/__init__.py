@@ -11,6 +11,8 @@ tests read like the reference (line numbers into the reference repo):
                              fast pieces of larger ones too)
   search_first(msg, lower, upper, target)
                              the smallest nonce whose hash is <= target
+  search_first_multi(msg, lower, upper, target, devs)
+                             the same over several devices, chunk by chunk in ascending order
   search_hits(msg, lower, upper, target, cap=4096)
                              every nonce whose hash is <= target, and how many there are
   search_first_hits(msg, lower, upper, target, k)
@@ -30,6 +32,9 @@ tests read like the reference (line numbers into the reference repo):
                              chunks a miner may hold at once, so small Requests reach it as a batch)
   Message / NewRequest / NewResult / NewJoin / marshal / unmarshal
                              bitcoin/message.go:7-62 with Go encoding/json bytes
+  NewTargetRequest(data, lower, upper, target)
+                             a Request with the optional Target key: the first-hit question through the
+                             server, its miners and the client (Scheduler.submit_first)
   miner_handle(request)      one miner step: Request payload -> Result payload
 
 All compute goes through the C-ABI; there is no host fallback.
@@ -47,6 +52,7 @@ from ._lib import mh_first_request, mh_first_result, MH_FIRST_STOP_RUNNING  # no
 from ._lib import mh_hit, mh_hits, MH_HITS_MAX_CAP, mh_first_hits  # noqa: F401
 from ._lib import mh_hits_request, mh_hits_result, mh_hits_region  # noqa: F401
 from ._lib import mh_first_hits_request, mh_first_hits_result  # noqa: F401
+from ._lib import mh_message_ex, mh_sched_first_stats  # noqa: F401
 
 U64_MAX = (1 << 64) - 1
 
@@ -132,6 +138,21 @@ def search_multi(msg, lower, upper, devs=None, chunk=0):
     _check(lib.mh_search_multi(arr, len(devs), m, len(m), lower, upper, chunk, ctypes.byref(h),
                                ctypes.byref(n)))
     return h.value, n.value
+
+
+def search_first_multi(msg, lower, upper, target, devs=None, chunk=0, stop_running=False):
+    """search_first over the listed devices (default: every device), chunk by chunk through a target
+    job of the scheduler: (found, hash, nonce, scanned) with found, hash and nonce exactly
+    search_first's; scanned sums the chunks that completed, those above the hit included
+    (mh_search_first_multi).  chunk = 0: 2^30 nonces, the scheduler's default, not tuned."""
+    m = _b(msg)
+    if devs is None:
+        devs = list(range(device_count()))
+    arr = (ctypes.c_int * max(1, len(devs)))(*devs)
+    out = mh_first()
+    _check(lib.mh_search_first_multi(arr, len(devs), m, len(m), lower, upper, target, chunk,
+                                     MH_FIRST_STOP_RUNNING if stop_running else 0, ctypes.byref(out)))
+    return bool(out.found), out.hash, out.nonce, out.scanned
 
 
 def _requests(requests):
@@ -518,13 +539,15 @@ Join, Request, Result = 0, 1, 2  # MsgType iota, message.go:9-13
 
 
 class Message:
-    """bitcoin.Message (message.go:18-23)."""
+    """bitcoin.Message (message.go:18-23), plus the optional Target of a Request (None: absent;
+    include/minehip.h mh_message_ex)."""
 
-    __slots__ = ("Type", "Data", "Lower", "Upper", "Hash", "Nonce")
+    __slots__ = ("Type", "Data", "Lower", "Upper", "Hash", "Nonce", "Target")
 
-    def __init__(self, Type=0, Data=b"", Lower=0, Upper=0, Hash=0, Nonce=0):  # noqa: N803
+    def __init__(self, Type=0, Data=b"", Lower=0, Upper=0, Hash=0, Nonce=0, Target=None):  # noqa: N803
         self.Type, self.Data = Type, _b(Data)
         self.Lower, self.Upper, self.Hash, self.Nonce = Lower, Upper, Hash, Nonce
+        self.Target = Target
 
     def __eq__(self, o):
         return isinstance(o, Message) and all(getattr(self, k) == getattr(o, k) for k in self.__slots__)
@@ -546,6 +569,11 @@ def NewRequest(data, lower, upper):  # noqa: N802  (message.go:27-34)
     return Message(Request, data, lower, upper)
 
 
+def NewTargetRequest(data, lower, upper, target):  # noqa: N802
+    """A Request asking for the smallest nonce of [lower, upper] whose hash is <= target."""
+    return Message(Request, data, lower, upper, Target=target)
+
+
 def NewResult(hash_, nonce):  # noqa: N802  (message.go:38-44)
     return Message(Result, b"", 0, 0, hash_, nonce)
 
@@ -557,6 +585,12 @@ def NewJoin():  # noqa: N802  (message.go:47-49)
 def marshal(m):
     """json.Marshal(m) as Go produces it."""
     need = ctypes.c_size_t()
+    if m.Target is not None:  # the six reference keys, then "Target" (mh_msg_encode_ex)
+        args = (m.Type, m.Data, len(m.Data), m.Lower, m.Upper, m.Hash, m.Nonce, 1, m.Target)
+        lib.mh_msg_encode_ex(*args, None, 0, ctypes.byref(need))
+        buf = ctypes.create_string_buffer(need.value)
+        _check(lib.mh_msg_encode_ex(*args, buf, need.value, ctypes.byref(need)))
+        return buf.raw[:need.value]
     lib.mh_msg_encode(m.Type, m.Data, len(m.Data), m.Lower, m.Upper, m.Hash, m.Nonce, None, 0,
                       ctypes.byref(need))
     buf = ctypes.create_string_buffer(need.value)
@@ -568,11 +602,12 @@ def marshal(m):
 def unmarshal(payload):
     """json.Unmarshal(payload, &m) with Go's decoding rules."""
     p = _b(payload)
-    mm = mh_message()
+    mm = mh_message_ex()
     cap = len(p) + 16
     data = ctypes.create_string_buffer(cap)
-    _check(lib.mh_msg_decode(p, len(p), ctypes.byref(mm), data, cap))
-    return Message(mm.type, data.raw[:mm.data_len], mm.lower, mm.upper, mm.hash, mm.nonce)
+    _check(lib.mh_msg_decode_ex(p, len(p), ctypes.byref(mm), data, cap))
+    return Message(mm.type, data.raw[:mm.data_len], mm.lower, mm.upper, mm.hash, mm.nonce,
+                   mm.target if mm.has_target else None)
 
 
 def miner_handle(request_payload, devs=(0,)):
@@ -658,6 +693,12 @@ def _stats(fn, h):
     return {f: int(getattr(st, f)) for f, _ in mh_sched_stats._fields_}
 
 
+def _first_stats(fn, h):
+    st = mh_sched_first_stats()
+    _check(fn(h, ctypes.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in mh_sched_first_stats._fields_}
+
+
 def _chk_neg(rc):
     if rc < 0:
         _check(rc)
@@ -697,6 +738,22 @@ class Scheduler:
     def submit(self, client, msg, lower, upper):
         m = _b(msg)
         return _chk_neg(lib.mh_sched_submit(self._h, client, m, len(m), lower, upper))
+
+    def submit_first(self, client, msg, lower, upper, target):
+        """A target job: the smallest nonce of [lower, upper] whose hash is <= target
+        (mh_sched_submit_first); its completion is that hit, or the minimum when none qualifies."""
+        m = _b(msg)
+        return _chk_neg(lib.mh_sched_submit_first(self._h, client, m, len(m), lower, upper, target))
+
+    def job_target(self, job):
+        """The job's target, or None for a plain job (mh_sched_job_target)."""
+        has = ctypes.c_int()
+        t = ctypes.c_uint64()
+        _check(lib.mh_sched_job_target(self._h, job, ctypes.byref(has), ctypes.byref(t)))
+        return t.value if has.value else None
+
+    def first_stats(self):
+        return _first_stats(lib.mh_sched_first_stats_read, self._h)
 
     def drop_client(self, client):
         return _chk_neg(lib.mh_sched_drop_client(self._h, client))
@@ -783,3 +840,6 @@ class Server:
 
     def stats(self):
         return _stats(lib.mh_server_stats, self._h)
+
+    def first_stats(self):
+        return _first_stats(lib.mh_server_first_stats, self._h)

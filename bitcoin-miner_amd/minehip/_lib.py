@@ -45,6 +45,7 @@ EXPORTS = (
     "mh_miner_handle_batch_ex", "mh_search_first_ex", "mh_search_first_batch_stop",
     "mh_search_first_hits", "mh_first_hits_slices", "mh_first_hits_bound",
     "mh_search_first_hits_batch", "mh_first_hits_batch_regions",
+    "mh_msg_encode_ex", "mh_msg_decode_ex", "mh_search_first_multi",
     # minehip_server.h
     "mh_sched_default_opts", "mh_sched_create", "mh_sched_destroy", "mh_sched_add_miner",
     "mh_sched_remove_miner", "mh_sched_submit", "mh_sched_drop_client", "mh_sched_next",
@@ -52,6 +53,7 @@ EXPORTS = (
     "mh_server_create", "mh_server_destroy", "mh_server_read", "mh_server_lost",
     "mh_server_pop_write", "mh_server_stats",
     "mh_sched_default_queue_opts", "mh_sched_create_ex", "mh_server_create_ex", "mh_sched_miner_queue",
+    "mh_sched_submit_first", "mh_sched_job_target", "mh_sched_first_stats_read", "mh_server_first_stats",
 )
 
 
@@ -158,6 +160,11 @@ class mh_message(ctypes.Structure):
                 ("hash", ctypes.c_uint64), ("nonce", ctypes.c_uint64), ("data_len", ctypes.c_size_t)]
 
 
+class mh_message_ex(ctypes.Structure):
+    _fields_ = mh_message._fields_ + [("has_target", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                                      ("target", ctypes.c_uint64)]
+
+
 class mh_sched_opts(ctypes.Structure):
     _fields_ = [("init_chunk", ctypes.c_uint64), ("min_chunk", ctypes.c_uint64),
                 ("max_chunk", ctypes.c_uint64), ("target_ns", ctypes.c_uint64)]
@@ -181,6 +188,10 @@ class mh_sched_stats(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint64) for f in (
         "miners", "idle_miners", "jobs", "chunks_assigned", "chunks_done", "chunks_requeued",
         "nonces_done", "jobs_done", "jobs_cancelled")]
+
+
+class mh_sched_first_stats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("jobs_first", "jobs_found", "nonces_dropped", "results_ignored")]
 
 
 def _load():
@@ -208,6 +219,11 @@ def _load():
     L.mh_msg_encode.argtypes = [ctypes.c_int64, u8p, sz, u64, u64, u64, u64, ctypes.c_char_p, sz,
                                 ctypes.POINTER(sz)]
     L.mh_msg_decode.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(mh_message), ctypes.c_char_p, sz]
+    L.mh_msg_encode_ex.argtypes = [ctypes.c_int64, u8p, sz, u64, u64, u64, u64, ctypes.c_int, u64, ctypes.c_char_p, sz,
+                                   ctypes.POINTER(sz)]
+    L.mh_msg_decode_ex.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(mh_message_ex), ctypes.c_char_p, sz]
+    L.mh_search_first_multi.argtypes = [intp, ctypes.c_int, u8p, sz, u64, u64, u64, u64, ctypes.c_uint32,
+                                        ctypes.POINTER(mh_first)]
     L.mh_miner_handle.argtypes = [intp, ctypes.c_int, ctypes.c_char_p, sz, ctypes.c_char_p, sz,
                                   ctypes.POINTER(sz)]
     L.mh_profile_enable.argtypes = [ctypes.c_int, ctypes.c_int]
@@ -270,6 +286,10 @@ def _load():
     L.mh_sched_add_miner.argtypes = [vp, i64]
     L.mh_sched_remove_miner.argtypes = [vp, i64]
     L.mh_sched_submit.argtypes = [vp, i64, u8p, sz, u64, u64]
+    L.mh_sched_submit_first.argtypes = [vp, i64, u8p, sz, u64, u64, u64]
+    L.mh_sched_job_target.argtypes = [vp, i64, intp, u64p]
+    L.mh_sched_first_stats_read.argtypes = [vp, ctypes.POINTER(mh_sched_first_stats)]
+    L.mh_server_first_stats.argtypes = [vp, ctypes.POINTER(mh_sched_first_stats)]
     L.mh_sched_drop_client.argtypes = [vp, i64]
     L.mh_sched_next.argtypes = [vp, i64, u64, ctypes.POINTER(mh_assignment)]
     L.mh_sched_job_msg.argtypes = [vp, i64, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
@@ -286,7 +306,7 @@ def _load():
                "mh_first_batch_order": ctypes.c_int64, "mh_hits_batch_regions": ctypes.c_int64,
                "mh_first_batch_order_ex": ctypes.c_int64, "mh_hits_batch_regions_ex": ctypes.c_int64,
                "mh_first_hits_batch_regions": ctypes.c_int64,
-               "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64,
+               "mh_last_error": ctypes.c_char_p, "mh_sched_submit": i64, "mh_sched_submit_first": i64,
                "mh_sched_create": vp, "mh_server_create": vp, "mh_sched_default_opts": None,
                "mh_sched_create_ex": vp, "mh_server_create_ex": vp, "mh_sched_default_queue_opts": None,
                "mh_sched_miner_queue": i64, "mh_first_hits_bound": u64,

@@ -167,8 +167,8 @@ typedef struct mh_first {
  * target == 2^64-1 makes every nonce qualify (the answer is lower); target == 0 only a zero hash.
  * Errors and calling conventions as mh_search: MH_ERANGE, MH_ETOOLONG, MH_EINVAL (out == NULL
  * too), MH_ENODEV.  Additive in ABI 5 (no existing struct changes).
- * Out of scope: a multi-device form, and the LSP protocol, which stays as it is (the reference's
- * Message has no target field).  The batched form is mh_search_first_batch below. */
+ * The multi-device form is mh_search_first_multi, the batched form mh_search_first_batch, both
+ * below; through the LSP protocol the question is a Request with a Target (mh_message_ex). */
 int mh_search_first(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                     uint64_t target, mh_first *out);
 
@@ -192,6 +192,23 @@ int mh_search_first(int dev, const uint8_t *msg, size_t len, uint64_t lower, uin
 #define MH_FIRST_STOP_RUNNING 1u
 int mh_search_first_ex(int dev, const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper,
                        uint64_t target, uint32_t flags, mh_first *out);
+
+/* mh_search_first over the listed devices: one host thread per entry of devs, each taking the
+ * next chunk of `chunk` nonces from a target job of the server's scheduler (minehip_server.h:
+ * chunks in ascending order, nothing handed out above a known hit, done once everything below
+ * the hit is answered) and running mh_search_first_ex(devs[i], ..., flags) on it.
+ * flags: 0 or MH_FIRST_STOP_RUNNING; any other bit is MH_EINVAL before a device is touched.
+ * chunk == 0 means 2^30, the scheduler's own init_chunk default; it is not tuned for this call.
+ * found, hash and nonce are bit for bit mh_search_first's, whatever the chunk, the number of
+ * workers or the timing.  scanned is the sum of scanned over the chunks that completed, those
+ * above the hit included: nonce - lower + 1 <= scanned <= upper - lower + 1 when found, and
+ * upper - lower + 1 when not.
+ * A device that fails hands its chunk back to the others, as in mh_search_multi's fixed-chunk
+ * mode; the call fails only if every worker fails (with the first failure's code).  A list may
+ * repeat a device and holds at most MH_MAX_WORKERS entries.  Errors as mh_search_first, plus
+ * MH_EINVAL for a bad device list.  Additive in ABI 5. */
+int mh_search_first_multi(const int *devs, int ndev, const uint8_t *msg, size_t len, uint64_t lower,
+                          uint64_t upper, uint64_t target, uint64_t chunk, uint32_t flags, mh_first *out);
 
 /* ---- batched first-hit search: many small proof-of-work questions at once ---- */
 
@@ -508,6 +525,34 @@ int mh_msg_encode(int64_t type, const uint8_t *data, size_t dlen, uint64_t lower
  * if data_cap is short (out->data_len still set), MH_EINVAL on bad JSON. */
 int mh_msg_decode(const char *json, size_t len, mh_message *out, uint8_t *data, size_t data_cap);
 
+/* A Message with the optional Target of a Request: the proof-of-work question (mh_search_first)
+ * through the protocol.  The reference's Message has no such field, and needs none to stay
+ * compatible: Go's json.Unmarshal ignores unknown keys, so every reference endpoint reads a
+ * Request that carries "Target" as a plain Request.  (In Go the field is
+ *     Target *uint64 `json:",omitempty"`
+ * as the last field of bitcoin.Message; INTEGRATION.md.)  A Result has no new field: a chunk
+ * with a hit answers with that hit, one without with its minimum, and whoever merges tells them
+ * apart by hash <= target. */
+typedef struct mh_message_ex {
+    int64_t type;
+    uint64_t lower, upper;
+    uint64_t hash, nonce;
+    size_t data_len;
+    int32_t has_target, reserved; /* 1: the payload has a "Target" key that is not null */
+    uint64_t target;              /* its value; 0 without one */
+} mh_message_ex;
+
+/* mh_msg_encode, and when has_target != 0 `,"Target":<target>` as a seventh and last key.  With
+ * has_target == 0 the bytes are mh_msg_encode's.  Additive in ABI 5. */
+int mh_msg_encode_ex(int64_t type, const uint8_t *data, size_t dlen, uint64_t lower, uint64_t upper,
+                     uint64_t hash, uint64_t nonce, int has_target, uint64_t target, char *out, size_t cap,
+                     size_t *out_len);
+
+/* mh_msg_decode that also reads the key "Target" (case-insensitive, as every key): a uint64,
+ * refused (MH_EINVAL) when malformed, negative, fractional or above 2^64-1, exactly as Lower is;
+ * null counts as absent.  mh_msg_decode itself ignores the key.  Additive in ABI 5. */
+int mh_msg_decode_ex(const char *json, size_t len, mh_message_ex *out, uint8_t *data, size_t data_cap);
+
 /* One step of the GPU miner (miner.go:33 TODO, spec SURVEY.md §8(a) A2):
  * decode a Request payload, search [Lower, Upper] on the listed devices,
  * encode NewResult(hash, nonce) (message.go:38-44) into out.  The Go miner
@@ -515,7 +560,11 @@ int mh_msg_decode(const char *json, size_t len, mh_message *out, uint8_t *data, 
  * the payload is not a JSON bitcoin.Message of type Request, MH_ERANGE when
  * its Lower > Upper: a miner skips those.  Any other error comes from the
  * search itself (MH_EHIP, MH_EINTERNAL, ...): the miner should exit, so the
- * server's lost-miner path hands the chunk to another miner. */
+ * server's lost-miner path hands the chunk to another miner.
+ * A Request with a Target (mh_message_ex) is answered by NewResult(hash, nonce) of the first-hit
+ * search of [Lower, Upper]: mh_search_first_ex on one listed device, mh_search_first_multi
+ * (chunk 0) on several -- the chunk's smallest qualifying nonce, or its minimum when none
+ * qualifies, which is what the server's target jobs rely on (minehip_server.h). */
 int mh_miner_handle(const int *devs, int ndev, const char *request, size_t len, char *out, size_t cap,
                     size_t *out_len);
 
@@ -527,7 +576,12 @@ int mh_miner_handle(const int *devs, int ndev, const char *request, size_t len, 
  * Returns MH_OK when every payload has a status (MH_OK: answer with the Result; MH_ENOTREQ,
  * MH_ERANGE: skip; MH_EINVAL: cap_each is short, out_lens[i] is the size needed); a device-level
  * failure of a search (MH_ENODEV, MH_EHIP, MH_EINTERNAL) is the call's return code: the miner
- * should exit.  out_lens may be NULL. */
+ * should exit.  out_lens may be NULL.
+ * When some payload carries a Target (mh_message_ex), the plain Requests go where they go
+ * otherwise and the Target Requests through one mh_search_first_batch_ex on devs[0] (with
+ * MH_BATCH_FUSE_FAST when mh_miner_handle_batch_ex was given it; the requests that call runs as
+ * fallbacks take its own fallback path).  Statuses and Results stay in payload order, each bit
+ * for bit mh_miner_handle's for that payload.  A list without a Target runs as it always did. */
 int mh_miner_handle_batch(const int *devs, int ndev, const char *const *requests, const size_t *lens, size_t n,
                           char *out, size_t cap_each, size_t *out_lens, int *status);
 

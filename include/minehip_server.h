@@ -91,6 +91,44 @@ int mh_sched_remove_miner(mh_sched *s, int64_t miner);
 int64_t mh_sched_submit(mh_sched *s, int64_t client, const uint8_t *msg, size_t len, uint64_t lower,
                         uint64_t upper);
 
+/* ---- target jobs: the proof-of-work question (mh_search_first) through the scheduler ----
+ *
+ * A client's Request with a Target (minehip.h mh_message_ex): the answer is the smallest nonce n
+ * of [lower, upper] with Hash(msg, n) <= target and its hash, or the range's minimum when no nonce
+ * qualifies -- exactly mh_search_first's found / hash / nonce, with found = (hash <= target).
+ * Returns the new job id (>= 0) or MH_E*.  A job from mh_sched_submit behaves as it always did.
+ *   Hand-out order.  The pending chunk with the lowest nonces goes out first: requeued chunks in
+ *     ascending order of their first nonce (they always lie below the fresh nonces), then fresh
+ *     nonces.  Sizing, round-robin over jobs, eligibility and queue depth are unchanged.
+ *   Results.  A Result with hash <= target is a hit at its nonce; the job keeps the hit with the
+ *     smallest nonce, b.  A Result without a hit feeds the lexicographic minimum.
+ *   Once a hit is known, nothing above b is handed out: the fresh remainder is dropped, requeued
+ *     chunks that start above b are dropped, and a lost miner's chunk that starts above b is not
+ *     requeued.
+ *   Completion.  The job completes the moment a hit exists and no pending or outstanding chunk
+ *     starts below b; mh_completion's hash / nonce are the hit at b.  It does not wait for the
+ *     chunks still out above the hit (the protocol has no message to recall them): the job stays
+ *     on, finished and draining, until they are back, and their late Results are validated as any
+ *     other, counted off and ignored (mh_sched_result returns 0).  Without a hit the job completes
+ *     when every chunk is back, with the minimum.
+ *   Validation of Results is unchanged (nonce in the chunk; at depth > 1 the host Hash check that
+ *     removes the miner); MH_ERANGE / MH_EREJECTED on a chunk of a finished job only counts it off.
+ * Why the answer is mh_search_first's whatever the chunking, the order, the depth or the losses:
+ * let n* be the smallest qualifying nonce of the range and C the chunk that holds it.  C's miner
+ * returns n*, the smallest qualifying nonce in C; every reported hit is >= n*; and the job cannot
+ * complete on a hit b > n* while C is pending or out, because C's first nonce <= n* < b.
+ * This needs every miner to answer a chunk that carries a Target as mh_miner_handle does: with the
+ * chunk's FIRST hit.  A reference Go miner ignores the key and returns the chunk's minimum -- a hit
+ * if the chunk has one, but not necessarily its first.  In a mixed cluster the job still completes
+ * with a qualifying nonce whenever one exists, but not always the smallest. */
+int64_t mh_sched_submit_first(mh_sched *s, int64_t client, const uint8_t *msg, size_t len, uint64_t lower,
+                              uint64_t upper, uint64_t target);
+
+/* *has_target = 1 and *target for a job from mh_sched_submit_first, 0 and 0 for one from
+ * mh_sched_submit: what the server needs to encode the chunk Requests (mh_assignment does not
+ * carry it).  MH_EINVAL for an unknown job or a NULL pointer. */
+int mh_sched_job_target(mh_sched *s, int64_t job, int *has_target, uint64_t *target);
+
 /* A client was lost: its jobs are cancelled; chunks already out are ignored
  * when they come back.  Returns the number of jobs cancelled. */
 int mh_sched_drop_client(mh_sched *s, int64_t client);
@@ -142,6 +180,16 @@ typedef struct mh_sched_stats {
 
 int mh_sched_stats_read(mh_sched *s, mh_sched_stats *out);
 
+/* Counters of the target jobs (mh_sched_stats itself does not grow). */
+typedef struct mh_sched_first_stats {
+    uint64_t jobs_first;      /* jobs from mh_sched_submit_first */
+    uint64_t jobs_found;      /* of those, completed with a hit */
+    uint64_t nonces_dropped;  /* nonces never handed out because they lay above a hit */
+    uint64_t results_ignored; /* late Results of finished jobs */
+} mh_sched_first_stats;
+
+int mh_sched_first_stats_read(mh_sched *s, mh_sched_first_stats *out);
+
 /* ---- the server loop (server.go:62 TODO) ------------------------------ */
 
 typedef struct mh_server mh_server;
@@ -160,7 +208,10 @@ void mh_server_destroy(mh_server *v);
  * connection (lsp.Server.CloseConn) so the client sees it end instead of
  * waiting forever for a Result.  MH_EREJECTED also for a miner's Result that
  * mh_sched_result refused at depth > 1: the miner is gone from the server and
- * its chunks are handed out again; close that connection too. */
+ * its chunks are handed out again; close that connection too.
+ * A client Request with a Target becomes a target job (mh_sched_submit_first): its chunk Requests
+ * carry the Target, and the client gets a plain Result -- the first hit, or the minimum when
+ * nothing qualifies; the client tells them apart by hash <= target. */
 int mh_server_read(mh_server *v, int64_t conn, const char *payload, size_t len, uint64_t now_ns);
 
 /* lsp.Server.Read returned (conn, nil, err): the connection is lost. */
@@ -172,6 +223,7 @@ int mh_server_lost(mh_server *v, int64_t conn, uint64_t now_ns);
 int mh_server_pop_write(mh_server *v, int64_t *conn, char *out, size_t cap, size_t *len);
 
 int mh_server_stats(mh_server *v, mh_sched_stats *out);
+int mh_server_first_stats(mh_server *v, mh_sched_first_stats *out);
 
 #ifdef __cplusplus
 }
